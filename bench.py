@@ -8,16 +8,25 @@ pair counting sort, M merge iterations (count deltas -> argmax -> merge), the
 final ids compacted in HBM.  `--steps K` jobs are timed back to back after
 `--warmup W` untimed jobs; the merge count does not depend on K.
 
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) sets up, warms up, times
+the K jobs and prints the result line: value, ms_per_step, the correctness
+digests and the roofline objects that come out of the timed jobs' own counters.
+`--dump-outputs DIR` also writes what the last timed job computed (below).
+Every leg that takes runs of its own is behind `--full`: the 1024-merge,
+ingest and configs[1] figures, the CPU baselines, the 1 -> N speed-up and weak
+scaling legs and the configs[4] encode measurement (`--no-extras`,
+`--no-cpu-baseline` and `--no-encode` switch single legs of `--full` off).
+
   N = 1  BASELINE configs[2]: 1 GiB x 8192 merges on one MI355X (the "HBM
          roofline run").  Extra key `train_1024`: the same corpus at 1024
-         merges (configs[3] at N = 1, the north-star comparison point).
+         merges (configs[3] at N = 1, the north-star comparison point; --full).
   N > 1  BASELINE configs[3]: the SAME 1 GiB corpus cut into N contiguous
          shards, one per rank (strong scaling), 1024 merges; per merge a sum
          of count deltas + a gather of edge records over xGMI (P2P mailboxes,
-         or RCCL with --xport rccl).  Rank 0 first times the single-GPU job on
-         its own device, so the line carries the measured speed-up 1 -> N and
-         checks that merges and ids (checksum) equal the single-GPU run.
-         Extra key `weak`: N GiB (1 GiB per rank), one job.
+         or RCCL with --xport rccl).  With --full rank 0 first times the
+         single-GPU job on its own device, so the line carries the measured
+         speed-up 1 -> N and checks that merges and ids (checksum) equal the
+         single-GPU run; extra key `weak`: N GiB (1 GiB per rank), one job.
 
 value = corpus_MB * merges * K / wall  (MB = 1e6 bytes; whole job, max over ranks)
 
@@ -35,11 +44,27 @@ The line also carries
   correctness     merges md5 + position-keyed ids checksum (bpe_gpu_ids_checksum)
                   of the warm-up and the timed jobs: they must agree, else the
                   line carries "error" and the process exits non-zero;
-  cpu_baseline    the unmodified reference (oracle/_ref/bpe_ref, 16 pthreads as
-                  it hard-codes) on a bounded sample, rank 0 at N = 1 only;
-  encode          BASELINE configs[4]: a 10 GiB seed-3 stream through the first
-                  32768 merges the trainer learns; ids checksum of the warm and
-                  timed runs must agree and n_out + occurrences == bytes.
+  cpu_baseline    (--full) the unmodified reference (oracle/_ref/bpe_ref, 16
+                  pthreads as it hard-codes; without it the oracle port, one
+                  thread) on a bounded sample, rank 0 at N = 1 only;
+  encode          (--full) BASELINE configs[4]: a 10 GiB seed-3 stream through
+                  the first 32768 merges the trainer learns; ids checksum of
+                  the warm and timed runs must agree and n_out + occurrences
+                  == bytes.
+
+--dump-outputs DIR  what a caller of the timed path receives from the last
+  timed job, as float .npy files (every value is an integer below 2^53, so
+  the floats are exact), under 64 MB in all:
+    merges.npy            (M, 2) float64: the merge table (left id, right id)
+    ids_head.npy          float32: the first DUMP_HEAD ids of the compacted corpus
+    ids_sample_index.npy  float64: DUMP_SAMPLE sorted positions drawn with a
+                          fixed seed from [0, n_ids) (all of them if fewer)
+    ids_sample.npy        float32: the ids at those positions
+    ids_digest.npy        float64 [n_ids, checksum >> 32, checksum & 0xffffffff]:
+                          the position-keyed checksum over ALL ids
+  The corpus is a function of --seed / --size alone, so two builds run with
+  the same arguments can be compared file by file.  Sharded: rank 0 writes
+  its own shards' ids (n_ids and the checksum stay those of the whole corpus).
 """
 import argparse
 import csv
@@ -284,6 +309,27 @@ def committed_profile(name, sharded=False):
     return out
 
 
+DUMP_HEAD = 1 << 20
+DUMP_SAMPLE = 1 << 21
+
+
+def dump_outputs(path, merges, ids, n_ids, checksum):
+    """--dump-outputs: the last timed job's merges and ids (module docstring)"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    n = int(ids.size)
+    if n <= DUMP_SAMPLE:
+        idx = np.arange(n, dtype=np.int64)
+    else:
+        idx = np.unique(np.random.default_rng(20240607).integers(0, n, DUMP_SAMPLE, dtype=np.int64))
+    np.save(os.path.join(path, "merges.npy"), np.asarray(merges, dtype=np.float64).reshape(-1, 2))
+    np.save(os.path.join(path, "ids_head.npy"), ids[:DUMP_HEAD].astype(np.float32))
+    np.save(os.path.join(path, "ids_sample_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(path, "ids_sample.npy"), ids[idx].astype(np.float32))
+    np.save(os.path.join(path, "ids_digest.npy"),
+            np.array([n_ids, checksum >> 32, checksum & 0xFFFFFFFF], dtype=np.float64))
+
+
 def train_single(args, cx, out):
     """N = 1: configs[2] (1 GiB x 8192 merges) + the 1024-merge figure"""
     from llmtokenizer_amd import api
@@ -304,6 +350,8 @@ def train_single(args, cx, out):
         out["error"] = f"a job stopped early: {sorted(set(done))} merges"
     if ref is not None and ref != got:
         out["error"] = f"warm-up and timed jobs differ: {ref} vs {got}"
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, e.merges(), e.ids(), st["n_out"], got[1])
     extra = {}
     if not args.no_extras:
         e.train(1024)  # warm
@@ -432,6 +480,8 @@ def train_sharded(args, cx, out):
     csum, n_ids = group_checksum(cx, g)
     prof = g.kernel_profile(0)
     transport = g.transport()
+    if args.dump_outputs and cx.rank == 0:
+        dump_outputs(args.dump_outputs, g.merges(), g.all_ids(), n_ids, csum)
     if any(k != merges for k in done):
         out["error"] = f"a job stopped early: {sorted(set(done))} merges"
     if len(set(digests)) != 1:
@@ -547,7 +597,14 @@ def main():
     ap.add_argument("--encode-size", type=int, default=10 << 30)
     ap.add_argument("--encode-merges", type=int, default=32768)
     ap.add_argument("--cpu-encode-size", type=int, default=64 << 20)
+    ap.add_argument("--full", action="store_true",
+                    help="also the legs that take runs of their own: 1024-merge / ingest / configs[1] / speed-up / "
+                         "weak figures, CPU baselines, the configs[4] encode (default: the timed jobs only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed job's merges and ids (a fixed sample) as DIR/<name>.npy")
     args = ap.parse_args()
+    if not args.full:
+        args.no_extras = args.no_cpu_baseline = args.no_encode = True
 
     sharded = int(os.environ.get("WORLD_SIZE", "1")) > 1 or args.sharded
     cx = Ctx(sharded)

@@ -87,11 +87,9 @@ REF_FILES = {
 
 @pytest.mark.parametrize("fname", ["testing.txt", pytest.param("random_text.txt", marks=pytest.mark.slow)])
 def test_reference_corpus_hashes(fname):
-    """Hashes of the reference run on its own corpora; only in
-    the build container, where /root/reference exists."""
-    path = os.path.join("/root/reference", fname)
-    if not os.path.exists(path):
-        pytest.skip("reference corpus not present")
+    """Hashes of the reference run on its own corpora, the
+    corpora read from their committed copies (tests/golden/)."""
+    path = os.path.join(G.GOLD, fname)
     import hashlib
     m_md5, i_md5, cap = REF_FILES[fname]
     data = O.effective_bytes(open(path, "rb").read())

@@ -5,7 +5,7 @@
 set -o pipefail
 OUT=${OUT:-gpurun_out}
 TAG=${TAG:-ab}
-B="python bench.py --no-encode --no-cpu-baseline"
+B="python bench.py --full --no-encode --no-cpu-baseline"
 for rep in 1 2; do
     timeout -k 10 200 $B > $OUT/ab_new_${TAG}_$rep.json 2>/dev/null || exit 1
     BPE_LIB=ab/libbpe_head.so timeout -k 10 200 $B > $OUT/ab_head_${TAG}_$rep.json 2>/dev/null || exit 1
