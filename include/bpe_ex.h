@@ -42,7 +42,21 @@ dyn_arr_t *compress_multi(const char *path, long max_merges, int ngpu, uint32_t 
 /* encode bytes with a trained merge list (dyn_arr_t from compress/read_pairs) */
 uint32_t *bpe_encode_bytes(const uint8_t *bytes, size_t n, dyn_arr_t *pair_arr, int device, size_t *len);
 
-/* statistics of the last compress/compress_ex/bpe_train_bytes/bpe_encode_bytes */
+/* Encode a batch of documents in one pass: document d is bytes [doc_off[d],
+ * doc_off[d + 1]) (doc_off[0] == 0, doc_off[ndocs] == n, non-decreasing) and no
+ * merge crosses a document start, so ids [(*id_off)[d], (*id_off)[d + 1]) are
+ * bpe_encode_bytes of document d alone.  The caller frees the returned ids
+ * and *id_off (ndocs + 1 entries) with free(). */
+uint32_t *bpe_encode_docs(const uint8_t *bytes, size_t n, const uint64_t *doc_off, size_t ndocs,
+                          dyn_arr_t *pair_arr, int device, size_t *len, uint64_t **id_off);
+/* The inverse: the documents' bytes concatenated (NUL bytes vanish, as in
+ * decompress; NUL-terminated, *out_len without it) and *byte_off (ndocs + 1
+ * entries): document d is out [(*byte_off)[d], (*byte_off)[d + 1]).  The
+ * caller frees both with free(). */
+char *bpe_decode_docs(const uint32_t *ids, size_t len, const uint64_t *id_off, size_t ndocs,
+                      dyn_arr_t *pair_arr, int device, size_t *out_len, uint64_t **byte_off);
+
+/* statistics of the last compress/compress_ex/bpe_train_bytes/bpe_encode_bytes/bpe_encode_docs */
 int bpe_last_stats(bpe_gpu_stats *out);
 
 /* compress / compress_ex / bpe_train_bytes / bpe_encode_bytes / decompress keep

@@ -214,6 +214,34 @@ int bpe_gpu_decode(bpe_gpu_ctx *ctx, const uint32_t *ids, size_t len,
                    const uint32_t *pairs, size_t n_merges,
                    uint8_t *out, size_t cap, size_t *out_len);
 
+/* ------------------------------------------------------------------------
+ * Document batches.  A batch is the loaded bytes plus ndocs + 1 offsets:
+ * doc_off[0] == 0, doc_off[ndocs] == the loaded length, non-decreasing (empty
+ * documents are allowed); document d is bytes [doc_off[d], doc_off[d + 1]).
+ * Merges never cross a document start: the ids of document d are exactly
+ * bpe_gpu_encode's of its bytes alone, for any merge list that call accepts.
+ * One device, at most 2^32 - 2 bytes and documents per batch.
+ * ---------------------------------------------------------------------- */
+
+/* Encode the loaded bytes as ndocs documents (doc_off[ndocs + 1], see above).  Afterwards
+   bpe_gpu_fetch_ids / _fetch_ids_range / _ids_checksum serve the concatenated ids. */
+int bpe_gpu_encode_docs(bpe_gpu_ctx *ctx, const uint64_t *doc_off, size_t ndocs,
+                        const uint32_t *pairs, size_t n_merges);
+/* id_off[0..ndocs] of the last bpe_gpu_encode_docs; out may be NULL, *count = ndocs + 1 */
+int bpe_gpu_fetch_doc_offsets(bpe_gpu_ctx *ctx, uint64_t *out, size_t cap, size_t *count);
+/* out8 = {ndocs, docs through the fallback, windows, windows failed, core, halo, 0, 0} */
+int bpe_gpu_docs_info(bpe_gpu_ctx *ctx, uint64_t *out8);
+/* bpe_gpu_decode plus byte_off[0..ndocs] (bytes of document d = out[byte_off[d], byte_off[d+1])) */
+int bpe_gpu_decode_docs(bpe_gpu_ctx *ctx, const uint32_t *ids, size_t len, const uint64_t *id_off,
+                        size_t ndocs, const uint32_t *pairs, size_t n_merges,
+                        uint8_t *out, size_t cap, size_t *out_len, uint64_t *byte_off);
+/* The window geometry of the document encoder (pure function, no GPU; exported
+ * for the host-side tests): window w of cores of `core` bytes over the batch,
+ * clipped at the document starts around its core.
+ * out8 = {L, R, lunk, runk, first doc with off >= L, doc starts in [L, R], 0, 0} */
+int bpe_gpu_docs_window(const uint64_t *doc_off, size_t ndocs, uint64_t n,
+                        uint32_t core, uint32_t halo, uint64_t w, uint64_t *out8);
+
 int bpe_gpu_get_stats(bpe_gpu_ctx *ctx, bpe_gpu_stats *st);
 
 /* Position-keyed checksum of the ids of the last train / encode, computed in

@@ -21,7 +21,7 @@ EXPORTS = [
     "hash_table_search", "hash_table_clear", "hash_table_merge",
     # bpe_ex.h
     "compress_ex", "bpe_train_bytes", "bpe_encode_bytes", "bpe_last_stats",
-    "bpe_train_bytes_devices", "compress_multi", "bpe_release_engines",
+    "bpe_train_bytes_devices", "compress_multi", "bpe_release_engines", "bpe_encode_docs", "bpe_decode_docs",
     # bpe_gpu.h
     "bpe_gpu_device_count", "bpe_gpu_create", "bpe_gpu_destroy", "bpe_gpu_load", "bpe_gpu_synth",
     "bpe_gpu_train", "bpe_gpu_fetch_merges", "bpe_gpu_fetch_ids", "bpe_gpu_encode", "bpe_gpu_decode",
@@ -36,6 +36,9 @@ EXPORTS = [
     "bpe_gpu_group_create_local_p2p", "bpe_gpu_ids_checksum", "bpe_gpu_group_ids_checksum", "bpe_gpu_load_fd",
     "bpe_gpu_fetch_ids_range", "bpe_gpu_group_fetch_ids_range", "bpe_gpu_device_pci", "bpe_gpu_peer_access",
     "bpe_gpu_fetch_events", "bpe_gpu_trim",
+    # bpe_gpu.h: document batches
+    "bpe_gpu_encode_docs", "bpe_gpu_fetch_doc_offsets", "bpe_gpu_docs_info", "bpe_gpu_decode_docs",
+    "bpe_gpu_docs_window",
 ]
 
 
@@ -171,6 +174,18 @@ def load():
     L.bpe_last_stats.argtypes = [ctypes.POINTER(GpuStats)]
     L.bpe_gpu_fetch_events.argtypes = [vp, ctypes.POINTER(ctypes.c_uint64), sz, ctypes.POINTER(sz)]
     L.bpe_gpu_trim.argtypes = [vp]
+    u64p = ctypes.POINTER(ctypes.c_uint64)
+    L.bpe_gpu_encode_docs.argtypes = [vp, vp, sz, vp, sz]
+    L.bpe_gpu_fetch_doc_offsets.argtypes = [vp, vp, sz, ctypes.POINTER(sz)]
+    L.bpe_gpu_docs_info.argtypes = [vp, vp]
+    L.bpe_gpu_decode_docs.argtypes = [vp, vp, sz, vp, sz, vp, sz, vp, sz, ctypes.POINTER(sz), vp]
+    L.bpe_gpu_docs_window.argtypes = [vp, sz, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_uint64, vp]
+    L.bpe_encode_docs.argtypes = [vp, sz, vp, sz, ctypes.POINTER(DynArr), ctypes.c_int, ctypes.POINTER(sz),
+                                  ctypes.POINTER(u64p)]
+    L.bpe_encode_docs.restype = u32p
+    L.bpe_decode_docs.argtypes = [vp, sz, vp, sz, ctypes.POINTER(DynArr), ctypes.c_int, ctypes.POINTER(sz),
+                                  ctypes.POINTER(u64p)]
+    L.bpe_decode_docs.restype = ctypes.c_void_p
     L.bpe_release_engines.argtypes = []
     L.bpe_release_engines.restype = None
     _LIB = L

@@ -144,6 +144,58 @@ def encode(data: bytes, merges, device=0):
     return _take_ids(p, n.value)
 
 
+def _doc_offsets(offsets):
+    return np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
+
+
+def encode_batch(docs, merges, device=0):
+    """Encode a batch of documents (bytes-like objects) in one pass: no merge
+    crosses a document boundary.  Returns (ids, offsets): ids[offsets[d]:offsets[d + 1]]
+    equals encode(docs[d], merges); offsets is uint64 of length len(docs) + 1."""
+    L = _lib.load()
+    docs = [bytes(d) for d in docs]
+    buf = np.frombuffer(b"".join(docs), dtype=np.uint8)
+    off = np.zeros(len(docs) + 1, dtype=np.uint64)
+    off[1:] = np.cumsum(np.fromiter((len(d) for d in docs), dtype=np.uint64, count=len(docs)))
+    arr = _merges_to_arr(merges)
+    n = ctypes.c_size_t(0)
+    ido = ctypes.POINTER(ctypes.c_uint64)()
+    try:
+        p = L.bpe_encode_docs(buf.ctypes.data_as(ctypes.c_void_p), buf.size, off.ctypes.data_as(ctypes.c_void_p),
+                              len(docs), arr, int(device), ctypes.byref(n), ctypes.byref(ido))
+    finally:
+        L.dyn_arr_free(arr)
+    if not p:
+        raise BpeError("bpe_encode_docs failed")
+    offsets = np.ctypeslib.as_array(ido, shape=(len(docs) + 1,)).copy()
+    ctypes.CDLL(None).free(ctypes.cast(ido, ctypes.c_void_p))
+    return _take_ids(p, n.value), offsets
+
+
+def decode_batch(ids, offsets, merges, device=0):
+    """Inverse of encode_batch: the list of the documents' bytes (NUL bytes dropped, as decompress does)."""
+    L = _lib.load()
+    ids = np.ascontiguousarray(ids, dtype=np.uint32)
+    off = _doc_offsets(offsets)
+    if off.size < 1:
+        raise BpeError("decode_batch: offsets must hold len(docs) + 1 entries")
+    arr = _merges_to_arr(merges)
+    n = ctypes.c_size_t(0)
+    bo = ctypes.POINTER(ctypes.c_uint64)()
+    try:
+        p = L.bpe_decode_docs(ids.ctypes.data_as(ctypes.c_void_p), ids.size, off.ctypes.data_as(ctypes.c_void_p),
+                              off.size - 1, arr, int(device), ctypes.byref(n), ctypes.byref(bo))
+    finally:
+        L.dyn_arr_free(arr)
+    if not p:
+        raise BpeError("bpe_decode_docs failed")
+    raw = ctypes.string_at(p, n.value)
+    b = [int(bo[d]) for d in range(off.size)]
+    ctypes.CDLL(None).free(ctypes.c_void_p(p))
+    ctypes.CDLL(None).free(ctypes.cast(bo, ctypes.c_void_p))
+    return [raw[b[d]:b[d + 1]] for d in range(off.size - 1)]
+
+
 def decompress(ids, merges):
     """Reference decompress (bpe.c:341): bytes of the ids, NUL bytes dropped."""
     L = _lib.load()
@@ -229,6 +281,51 @@ class Engine:
     def encode(self, merges):
         m = np.ascontiguousarray(merges, dtype=np.uint32).reshape(-1)
         _lib.check(self.L.bpe_gpu_encode(self.ctx, m.ctypes.data_as(ctypes.c_void_p), m.size // 2), "encode")
+
+    def encode_docs(self, offsets, merges):
+        """encode the resident bytes as documents: document d is bytes
+        [offsets[d], offsets[d + 1]) (bpe_gpu_encode_docs); then ids(), doc_offsets(), docs_info()"""
+        off = _doc_offsets(offsets)
+        if off.size < 1:
+            raise BpeError("encode_docs: offsets must hold ndocs + 1 entries")
+        m = np.ascontiguousarray(merges, dtype=np.uint32).reshape(-1)
+        _lib.check(self.L.bpe_gpu_encode_docs(self.ctx, off.ctypes.data_as(ctypes.c_void_p), off.size - 1,
+                                              m.ctypes.data_as(ctypes.c_void_p), m.size // 2), "encode_docs")
+
+    def doc_offsets(self):
+        """id offsets of the last encode_docs (uint64, ndocs + 1 entries)"""
+        n = ctypes.c_size_t(0)
+        _lib.check(self.L.bpe_gpu_fetch_doc_offsets(self.ctx, None, 0, ctypes.byref(n)), "fetch_doc_offsets")
+        out = np.zeros(n.value, dtype=np.uint64)
+        _lib.check(self.L.bpe_gpu_fetch_doc_offsets(self.ctx, out.ctypes.data_as(ctypes.c_void_p), n.value,
+                                                    ctypes.byref(n)), "fetch_doc_offsets")
+        return out
+
+    DOCS_INFO = ("ndocs", "docs_fallback", "windows", "windows_failed", "core", "halo")
+
+    def docs_info(self):
+        """counters of the last encode_docs (bpe_gpu_docs_info)"""
+        out = np.zeros(8, dtype=np.uint64)
+        _lib.check(self.L.bpe_gpu_docs_info(self.ctx, out.ctypes.data_as(ctypes.c_void_p)), "docs_info")
+        return {k: int(out[i]) for i, k in enumerate(self.DOCS_INFO)}
+
+    def decode_docs(self, ids, offsets, merges):
+        """(bytes, byte offsets) of ids held as documents (bpe_gpu_decode_docs)"""
+        ids = np.ascontiguousarray(ids, dtype=np.uint32)
+        off = _doc_offsets(offsets)
+        if off.size < 1:
+            raise BpeError("decode_docs: offsets must hold ndocs + 1 entries")
+        m = np.ascontiguousarray(merges, dtype=np.uint32).reshape(-1)
+        n = ctypes.c_size_t(0)
+        vp = ctypes.c_void_p
+        args = (self.ctx, ids.ctypes.data_as(vp), ids.size, off.ctypes.data_as(vp), off.size - 1, m.ctypes.data_as(vp),
+                m.size // 2)
+        _lib.check(self.L.bpe_gpu_decode_docs(*args, None, 0, ctypes.byref(n), None), "decode_docs")
+        out = np.zeros(max(n.value, 1), dtype=np.uint8)
+        bo = np.zeros(off.size, dtype=np.uint64)
+        _lib.check(self.L.bpe_gpu_decode_docs(*args, out.ctypes.data_as(vp), out.size, ctypes.byref(n),
+                                              bo.ctypes.data_as(vp)), "decode_docs")
+        return out[: n.value].tobytes(), bo
 
     def merges(self):
         cnt = ctypes.c_size_t(0)
@@ -471,6 +568,22 @@ def shard_halo(records, me, a):
                                     out.ctypes.data_as(ctypes.c_void_p)), "shard_halo")
     return {"HL": [int(x) for x in out[0:3]], "HR": [int(x) for x in out[3:6]], "hlrun": int(out[6]),
             "myidx": int(out[7])}
+
+
+def docs_window(offsets, n, core, halo, w):
+    """window w of the document encoder over a batch of n bytes (pure host
+    function, bpe_gpu_docs_window): bytes [L, R), whether the neighbour beyond
+    each end exists (lunk / runk), the first document with offset >= L and the
+    document starts in [L, R]"""
+    L = _lib.load()
+    off = _doc_offsets(offsets)
+    if off.size < 1:
+        raise BpeError("docs_window: offsets must hold ndocs + 1 entries")
+    out = np.zeros(8, dtype=np.uint64)
+    _lib.check(L.bpe_gpu_docs_window(off.ctypes.data_as(ctypes.c_void_p), off.size - 1, int(n), int(core), int(halo),
+                                     int(w), out.ctypes.data_as(ctypes.c_void_p)), "docs_window")
+    return {"L": int(out[0]), "R": int(out[1]), "lunk": bool(out[2]), "runk": bool(out[3]), "first_doc": int(out[4]),
+            "doc_starts": int(out[5])}
 
 
 def device_count():

@@ -25,6 +25,7 @@
 #include "batch.hip"
 #include "encode.hip"
 #include "encode_win.hip"
+#include "encode_docs.hip"
 
 using namespace bpeamd;
 
@@ -289,6 +290,11 @@ struct bpe_gpu_ctx {
     bool loaded = false;
     bool ids_ready = false;
     uint64_t ids_len = 0;
+    // the last bpe_gpu_encode_docs: id offsets (device, [docs_n + 1]) and bpe_gpu_docs_info's counters
+    bool docs_ready = false;
+    uint64_t docs_n = 0;
+    uint64_t *d_idoff = nullptr;
+    uint64_t docs_info[8] = {};
     size_t merges_done = 0;
     std::vector<std::pair<void *, size_t>> train_allocs;  // live buffers of the current run
     std::vector<std::pair<void *, size_t>> pool;          // released buffers, reused by size
@@ -319,9 +325,10 @@ struct bpe_gpu_ctx {
     uint64_t prof_launches = 0;
     // grow-only device scratch of decode (ids, pairs, elen, offsets, scan
     // temporaries, output, error words; slots 0-6), of the window encoder
-    // (tables, halo bytes, rank exchange; 7-9), and the pinned staging of file loads
-    void *dscr[10] = {};
-    size_t dscr_cap[10] = {};
+    // (tables, halo bytes, rank exchange; 7-9), of bpe_gpu_decode_docs (id and byte offsets; 10-11),
+    // and the pinned staging of file loads
+    void *dscr[12] = {};
+    size_t dscr_cap[12] = {};
     std::vector<uint32_t> ew_stage;  // host image of the window encoder's tables (outlives the upload)
     uint8_t *stage[2] = {};
     hipEvent_t stage_ev[2] = {};
@@ -457,6 +464,7 @@ void free_train(bpe_gpu_ctx *c, bool release = false) {
         if (real_graph(g)) (void)hipGraphExecDestroy(g);
     c->retired.clear();
     c->ids_ready = false;
+    c->docs_ready = false;
 }
 
 int push_desc(bpe_gpu_ctx *c) {
@@ -2314,6 +2322,113 @@ int ew_run(bpe_gpu_ctx *c, const EwPlan &P, const uint32_t *d_img, uint32_t halo
     return 0;
 }
 
+// Encode c's bytes as documents (h_off[ndocs + 1], validated) by windows
+// (encode_docs.hip) into c's ids and id offsets; *nfail = windows whose core
+// came out uncertain, wfail = their flags (filled when there are any).
+int ed_run(bpe_gpu_ctx *c, const EwPlan &P, const uint32_t *d_img, uint32_t halo, const uint64_t *h_off, uint64_t ndocs,
+           uint64_t *nfail, std::vector<uint32_t> &wfail) {
+    const uint32_t core = EW_W - 2 * halo;
+    const uint64_t n = c->n0, nwin = (n + core - 1) / core;
+    int r;
+    uint32_t *ids, *cnt, *wfirst, *rel, *d_wfail;
+    uint16_t *stage;
+    unsigned long long *off;
+    uint64_t *d_doc, *d_idoff;
+    if ((r = dalloc(c, &ids, std::max<uint64_t>(n, 1), false))) return r;
+    if ((r = dalloc(c, &stage, std::max<uint64_t>(nwin * core, 1), false))) return r;
+    if ((r = dalloc(c, &cnt, nwin + 4))) return r;  // zeroed: counts (+ a 0 after the last), ticket, failed windows
+    if ((r = dalloc(c, &off, nwin + 1, false))) return r;
+    if ((r = dalloc(c, &wfirst, nwin + 1, false))) return r;
+    if ((r = dalloc(c, &d_wfail, std::max<uint64_t>(nwin, 1)))) return r;
+    if ((r = dalloc(c, &rel, ndocs + 1))) return r;
+    if ((r = dalloc(c, &d_doc, ndocs + 1, false))) return r;
+    if ((r = dalloc(c, &d_idoff, ndocs + 1, false))) return r;
+    const bool prof = getenv_int("BPE_EW_PROF", 0) != 0;  // (then the phases below are synchronised and timed)
+    double tph[4] = {now_ms(), 0, 0, 0};
+    HIPCHK(hipMemcpyAsync(d_doc, h_off, (ndocs + 1) * 8, hipMemcpyHostToDevice, c->st));
+    if (prof) {
+        HIPCHK(hipStreamSynchronize(c->st));
+        tph[1] = now_ms();
+    }
+    c->h.ids_out = ids;
+    c->d_idoff = d_idoff;
+    EncDocArgs D{};
+    EncWinArgs &A = D.w;
+    A.bytes = c->h.bytes;
+    A.n = n;
+    A.core = core;
+    A.halo = halo;
+    A.nwin = nwin;
+    A.nb = P.nb;
+    A.bp = d_img;
+    A.ht = (const unsigned long long *)(d_img + P.off_ht);
+    A.hmask = P.H - 1;
+    A.roles = d_img + P.off_roles;
+    A.bstart = d_img + P.off_bstart;
+    A.beq = (const uint8_t *)(d_img + P.off_beq);
+    A.stage = stage;
+    A.cnt = cnt;
+    A.ticket = cnt + nwin + 2;
+    A.fail = cnt + nwin + 3;
+    D.doc_off = d_doc;
+    D.wfirst = wfirst;
+    D.rel = rel;
+    D.wfail = d_wfail;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(nwin, (uint64_t)getenv_int("BPE_EW_GRID", 2048 * 256 / EW_T));
+    if (prof) {
+        if ((r = dalloc(c, &A.prof, 8 + 512))) return r;
+    }
+    k_ed_first<<<(uint32_t)((nwin + 256) / 256), 256, 0, c->st>>>(d_doc, ndocs, n, core, nwin, wfirst);
+    HIPCHK(hipGetLastError());
+    if (nwin) k_enc_docs<<<grid, EW_T, 0, c->st>>>(D);
+    HIPCHK(hipGetLastError());
+    if (prof) {
+        HIPCHK(hipStreamSynchronize(c->st));
+        tph[2] = now_ms();
+    }
+    size_t tb = 0;
+    HIPCHK(rocprim::exclusive_scan(nullptr, tb, cnt, off, 0ull, nwin + 1, rocprim::plus<unsigned long long>(), c->st));
+    void *tmp;
+    if ((r = dscratch(c, 4, tb, &tmp))) return r;
+    HIPCHK(rocprim::exclusive_scan(tmp, tb, cnt, off, 0ull, nwin + 1, rocprim::plus<unsigned long long>(), c->st));
+    k_ed_offsets<<<(uint32_t)((ndocs + 256) / 256), 256, 0, c->st>>>(d_doc, ndocs, n, core, off, nwin, rel, d_idoff);
+    HIPCHK(hipGetLastError());
+    if (nwin) {
+        const size_t glds = P.relabeled ? (size_t)P.V * 2 : 0;
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ew_gather), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)glds);
+        k_ew_gather<<<(uint32_t)std::min<uint64_t>((nwin + EWG_W - 1) / EWG_W, 512), EWG_T, glds, c->st>>>(
+            stage, cnt, off, nwin, core, P.relabeled ? d_img + P.off_unmap : nullptr, P.V, ids);
+    }
+    HIPCHK(hipGetLastError());
+    if (prof) {
+        unsigned long long h[8];
+        HIPCHK(hipMemcpyAsync(h, A.prof, sizeof h, hipMemcpyDeviceToHost, c->st));
+        HIPCHK(hipStreamSynchronize(c->st));
+        const double wn = (double)std::max(1ull, h[5]);
+        tph[3] = now_ms();
+        fprintf(stderr, "enc_docs phases (ms): offsets upload %.2f, first documents + windows %.2f, scan + offsets + gather %.2f\n",
+                tph[1] - tph[0], tph[2] - tph[1], tph[3] - tph[2]);
+        fprintf(stderr, "enc_docs: %llu windows, per window (us): init %.2f batches %.2f (merges %.2f, lookups %.2f) "
+                "output %.2f; batches with work %.1f of %u; lookup-list overflows %llu\n", h[5], h[0] / wn / 100.0,
+                h[1] / wn / 100.0, h[3] / wn / 100.0, h[7] / wn / 100.0, h[2] / wn / 100.0, h[4] / wn, P.nb, h[6]);
+    }
+    uint32_t fl = 0;
+    unsigned long long total = 0;
+    HIPCHK(hipMemcpyAsync(&fl, A.fail, 4, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipMemcpyAsync(&total, off + nwin, 8, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipStreamSynchronize(c->st));
+    *nfail = fl;
+    if (fl) {
+        wfail.resize(nwin);
+        HIPCHK(hipMemcpyAsync(wfail.data(), d_wfail, nwin * 4, hipMemcpyDeviceToHost, c->st));
+        HIPCHK(hipStreamSynchronize(c->st));
+    }
+    c->ids_len = total;
+    c->stats.enc_windows = nwin;
+    return 0;
+}
+
 }  // namespace
 
 // ===================================================================== C-ABI
@@ -3048,7 +3163,7 @@ int bpe_gpu_trim(bpe_gpu_ctx *c) {
     c->n0 = 0;
     c->loaded = false;
     c->pres_valid = false;
-    for (int k = 0; k < 10; k++) {
+    for (int k = 0; k < 12; k++) {
         if (c->dscr[k]) (void)hipFree(c->dscr[k]);
         c->dscr[k] = nullptr;
         c->dscr_cap[k] = 0;
@@ -3074,6 +3189,185 @@ int bpe_gpu_kernel_profile(bpe_gpu_ctx *c, const char **name, double *avg_ms, do
     if (avg_ms) *avg_ms = c->prof_ms;
     if (bytes_per_launch) *bytes_per_launch = c->prof_bytes;
     if (launches) *launches = c->prof_launches;
+    return 0;
+}
+
+// ------------------------------------------------ document batches (encode_docs.hip)
+
+int bpe_gpu_docs_window(const uint64_t *doc_off, size_t ndocs, uint64_t n, uint32_t core, uint32_t halo, uint64_t w,
+                        uint64_t *out8) {
+    if (!doc_off || !out8 || !core || ndocs > 0xFFFFFFFEull) return fail(BPE_GPU_EINVAL, "docs_window: bad argument");
+    if (doc_off[0] != 0 || doc_off[ndocs] != n) return fail(BPE_GPU_EINVAL, "docs_window: offsets must run from 0 to n");
+    for (size_t d = 0; d < ndocs; d++)
+        if (doc_off[d] > doc_off[d + 1]) return fail(BPE_GPU_EINVAL, "docs_window: offsets decrease");
+    if (w >= (n + core - 1) / core) return fail(BPE_GPU_EINVAL, "docs_window: no such window");
+    const uint64_t s0 = w * core, s1 = std::min<uint64_t>(n, s0 + core);
+    const EdGeom G = ed_geom(doc_off, n, core, halo, w, ed_lower(doc_off, ndocs, s0), ed_lower(doc_off, ndocs, s1));
+    const uint64_t first = ed_lower(doc_off, ndocs, G.L);
+    out8[0] = G.L;
+    out8[1] = G.R;
+    out8[2] = G.lunk;
+    out8[3] = G.runk;
+    out8[4] = first;
+    out8[5] = (uint64_t)(std::upper_bound(doc_off, doc_off + ndocs + 1, G.R) - doc_off) - first;
+    out8[6] = out8[7] = 0;
+    return 0;
+}
+
+int bpe_gpu_encode_docs(bpe_gpu_ctx *c, const uint64_t *doc_off, size_t ndocs, const uint32_t *pairs, size_t n_merges) {
+    if (!c || !doc_off || (!pairs && n_merges)) return BPE_GPU_EINVAL;
+    if (!c->loaded) return fail(BPE_GPU_ESTATE, "encode before load");
+    if (n_merges > 0xFFFFFEFFull) return fail(BPE_GPU_ERANGE, "merge list too long");
+    const uint64_t n = c->n0;
+    const double t_chk = now_ms();
+    if (ndocs > 0xFFFFFFFEull) return fail(BPE_GPU_EINVAL, "encode_docs: more than 2^32-2 documents");
+    if (doc_off[0] != 0) return fail(BPE_GPU_EINVAL, "encode_docs: the first offset is not 0");
+    if (doc_off[ndocs] != n) return fail(BPE_GPU_EINVAL, "encode_docs: the last offset is not the number of loaded bytes");
+    bool dec = false;  // (a reduction, not an early exit: 10^7 offsets are checked at memory speed)
+    for (size_t d = 0; d < ndocs; d++) dec |= doc_off[d] > doc_off[d + 1];
+    if (dec) return fail(BPE_GPU_EINVAL, "encode_docs: offsets decrease");
+    HIPCHK(hipSetDevice(c->dev));
+    c->stats = bpe_gpu_stats{};
+    c->stats.n_in = n;
+    c->fast = 0;
+    c->sharded = 0;
+    c->shard = 0;
+    c->nshards = 1;
+    const double t0 = now_ms();  // (the offset check above is outside: t_chk)
+    int r;
+    free_train(c);
+    // first pass: every window of the concatenated stream (nothing else runs when none fails)
+    std::vector<uint8_t> failed;  // documents for the fallback (sized when there are any)
+    uint64_t nfailed = 0, wfailed = 0, nwin = 0, core = 0, halo = 0;
+    bool first_pass = false;
+    const EwPlan P = n ? ew_plan(pairs, n_merges, c->ew_stage) : EwPlan{};
+    const double t_plan = now_ms();
+    if (P.ok) {
+        void *d_img;
+        if ((r = dscratch(c, 7, P.words * 4, &d_img))) return r;
+        HIPCHK(hipMemcpyAsync(d_img, c->ew_stage.data(), P.words * 4, hipMemcpyHostToDevice, c->st));
+        halo = ew_halo();
+        core = EW_W - 2 * halo;
+        nwin = (n + core - 1) / core;
+        std::vector<uint32_t> wfail;
+        if ((r = ed_run(c, P, (const uint32_t *)d_img, (uint32_t)halo, doc_off, ndocs, &wfailed, wfail))) return r;
+        first_pass = true;
+        if (wfailed) failed.assign(ndocs, 0);
+        if (wfailed)  // a document fails with any window holding one of its bytes in its core
+            for (size_t d = 0; d < ndocs; d++) {
+                if (doc_off[d] == doc_off[d + 1]) continue;
+                for (uint64_t w = doc_off[d] / core; w <= (doc_off[d + 1] - 1) / core && !failed[d]; w++) failed[d] = wfail[w] != 0;
+                nfailed += failed[d];
+            }
+    } else {
+        // no plan (too many merges or layers), or no bytes: every document with bytes goes through the fallback
+        failed.assign(ndocs, 0);
+        for (size_t d = 0; d < ndocs; d++) nfailed += failed[d] = doc_off[d] != doc_off[d + 1];
+    }
+    if (nfailed || !first_pass) {
+        // Fallback (cold): each failed document alone through bpe_gpu_encode on
+        // a helper context (exact for any input), spliced in through host
+        // memory; the result is made resident again.
+        std::vector<uint32_t> old_ids(first_pass ? c->ids_len : 0), ids;
+        std::vector<uint64_t> old_off(ndocs + 1, 0), id_off(ndocs + 1, 0);
+        if (first_pass) {
+            if (c->ids_len && (r = d2h_staged(c, old_ids.data(), c->h.ids_out, c->ids_len * 4))) return r;
+            if ((r = d2h_staged(c, old_off.data(), c->d_idoff, (ndocs + 1) * 8))) return r;
+        }
+        bpe_gpu_ctx *h = nullptr;
+        if (nfailed && (r = ctx_new(c->dev, nullptr, &h))) return r;
+        ids.reserve(old_ids.size());
+        for (size_t d = 0; d < ndocs && !r; d++) {
+            id_off[d] = ids.size();
+            if (!nfailed || !failed[d]) {
+                ids.insert(ids.end(), old_ids.begin() + old_off[d], old_ids.begin() + old_off[d + 1]);
+                continue;
+            }
+            const size_t len = doc_off[d + 1] - doc_off[d];
+            hipError_t e = hipSuccess;
+            if ((r = alloc_bytes(h, len))) break;
+            if ((e = hipMemcpyAsync(h->h.bytes, c->h.bytes + doc_off[d], len, hipMemcpyDeviceToDevice, h->st)) != hipSuccess ||
+                (e = hipStreamSynchronize(h->st)) != hipSuccess) {
+                r = fail(BPE_GPU_EHIP, "encode_docs: fallback copy", e);
+                break;
+            }
+            size_t k = 0;
+            if ((r = bpe_gpu_encode(h, pairs, n_merges)) || (r = bpe_gpu_fetch_ids(h, nullptr, 0, &k))) break;
+            const size_t at = ids.size();
+            ids.resize(at + k);
+            if (k) r = bpe_gpu_fetch_ids(h, ids.data() + at, k, &k);
+        }
+        id_off[ndocs] = ids.size();
+        bpe_gpu_destroy(h);
+        if (r) return r;
+        uint32_t *d_ids;
+        uint64_t *d_idoff;
+        if ((r = dalloc(c, &d_ids, std::max<size_t>(ids.size(), 1), false))) return r;
+        if ((r = dalloc(c, &d_idoff, ndocs + 1, false))) return r;
+        if (!ids.empty()) HIPCHK(hipMemcpyAsync(d_ids, ids.data(), ids.size() * 4, hipMemcpyHostToDevice, c->st));
+        HIPCHK(hipMemcpyAsync(d_idoff, id_off.data(), (ndocs + 1) * 8, hipMemcpyHostToDevice, c->st));
+        HIPCHK(hipStreamSynchronize(c->st));
+        c->h.ids_out = d_ids;
+        c->d_idoff = d_idoff;
+        c->ids_len = ids.size();
+    }
+    const double t1 = now_ms();
+    if (getenv_int("BPE_EW_PROF", 0))  // host phases (the kernel's own: ed_run, in an EW_PROF build)
+        fprintf(stderr, "encode_docs host (ms): offset check %.2f, plan %.2f, first pass + fallback %.2f\n", t0 - t_chk,
+                t_plan - t0, t1 - t_plan);
+    c->ids_ready = true;
+    c->docs_ready = true;
+    c->docs_n = ndocs;
+    const uint64_t info[8] = {ndocs, nfailed, nwin, wfailed, core, halo, 0, 0};
+    memcpy(c->docs_info, info, sizeof info);
+    c->merges_done = 0;
+    c->stats.enc_path = first_pass ? 1 : 2;
+    c->stats.enc_windows = nwin;
+    c->stats.n_out = c->ids_len;
+    c->stats.merges = n_merges;
+    c->stats.iterations = P.nb;
+    c->stats.occurrences = n - c->ids_len;
+    c->stats.ms_train = t1 - t0;
+    c->stats.ms_total = t1 - t0;
+    return 0;
+}
+
+int bpe_gpu_fetch_doc_offsets(bpe_gpu_ctx *c, uint64_t *out, size_t cap, size_t *count) {
+    if (!c || !count) return BPE_GPU_EINVAL;
+    if (!c->ids_ready || !c->docs_ready) return fail(BPE_GPU_ESTATE, "no document offsets: encode_docs first");
+    HIPCHK(hipSetDevice(c->dev));
+    *count = c->docs_n + 1;
+    const size_t k = out ? std::min<size_t>(cap, c->docs_n + 1) : 0;
+    if (k) return d2h_staged(c, out, c->d_idoff, k * 8);
+    return 0;
+}
+
+int bpe_gpu_docs_info(bpe_gpu_ctx *c, uint64_t *out8) {
+    if (!c || !out8) return BPE_GPU_EINVAL;
+    if (!c->ids_ready || !c->docs_ready) return fail(BPE_GPU_ESTATE, "no document batch: encode_docs first");
+    memcpy(out8, c->docs_info, sizeof c->docs_info);
+    return 0;
+}
+
+int bpe_gpu_decode_docs(bpe_gpu_ctx *c, const uint32_t *ids, size_t len, const uint64_t *id_off, size_t ndocs,
+                        const uint32_t *pairs, size_t n_merges, uint8_t *out, size_t cap, size_t *out_len,
+                        uint64_t *byte_off) {
+    if (!c || !out_len || !id_off || (!ids && len) || (!pairs && n_merges)) return BPE_GPU_EINVAL;
+    if (id_off[0] != 0 || id_off[ndocs] != len) return fail(BPE_GPU_EINVAL, "decode_docs: offsets must run from 0 to len");
+    for (size_t d = 0; d < ndocs; d++)
+        if (id_off[d] > id_off[d + 1]) return fail(BPE_GPU_EINVAL, "decode_docs: offsets decrease");
+    int r;
+    if ((r = bpe_gpu_decode(c, ids, len, pairs, n_merges, out, cap, out_len))) return r;
+    if (!byte_off) return 0;
+    // byte_off[d] = the ids' expansion-length prefix sum (left in scratch slot 3 by bpe_gpu_decode) at id_off[d]
+    void *d_idx, *d_out;
+    if ((r = dscratch(c, 10, (ndocs + 1) * 8, &d_idx)) || (r = dscratch(c, 11, (ndocs + 1) * 8, &d_out))) return r;
+    HIPCHK(hipMemcpyAsync(d_idx, id_off, (ndocs + 1) * 8, hipMemcpyHostToDevice, c->st));
+    k_ed_pick<<<(uint32_t)((ndocs + 256) / 256), 256, 0, c->st>>>((const uint64_t *)c->dscr[3], (const uint64_t *)d_idx,
+                                                                  ndocs + 1, (uint64_t *)d_out);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(byte_off, d_out, (ndocs + 1) * 8, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipStreamSynchronize(c->st));
     return 0;
 }
 

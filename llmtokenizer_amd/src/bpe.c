@@ -7,9 +7,7 @@
  * these functions report the error and return NULL, exactly like the
  * reference's own failure paths.
  */
-#include "../../include/bpe.h"
-#include "../../include/bpe_ex.h"
-#include "../../include/bpe_gpu.h"
+#include "bpe_internal.h"
 
 #include <pthread.h>
 #include <stdio.h>
@@ -19,7 +17,7 @@
 #include <time.h>
 #include <unistd.h>
 
-static bpe_gpu_stats g_last_stats;
+bpe_gpu_stats g_last_stats;
 
 bool is_less(const void *a, const void *b)
 {
@@ -191,7 +189,7 @@ static int env_int(const char *name, long dflt, long *out)
     return 0;
 }
 
-static void report(const char *what, int rc)
+void report(const char *what, int rc)
 {
     fprintf(stderr, "bpe: %s failed: %s (%s)\n", what, bpe_gpu_strerror(rc), bpe_gpu_last_error());
 }
@@ -217,7 +215,7 @@ static int keep_engines(void)
     return atoi(v) == 0 ? 0 : atoi(v) == 1 ? 2 : 1;
 }
 
-static int open_engine(int device, bpe_gpu_ctx **ctx)
+int open_engine(int device, bpe_gpu_ctx **ctx)
 {
     *ctx = NULL;
     if (device >= 0 && device < ENGINE_CACHE && keep_engines()) {
@@ -233,7 +231,7 @@ static int open_engine(int device, bpe_gpu_ctx **ctx)
 }
 
 /* back into the cache after a successful call, else destroyed */
-static void close_engine(int device, bpe_gpu_ctx *ctx, int ok)
+void close_engine(int device, bpe_gpu_ctx *ctx, int ok)
 {
     if (!ctx) return;
     const int keep = keep_engines();
@@ -274,7 +272,7 @@ static dyn_arr_t *pairs_to_arr(const uint32_t *pairs, size_t k)
 }
 
 /* reference-shaped merge list -> flat pairs for ids 256..last_index */
-static uint32_t *arr_to_pairs(dyn_arr_t *arr, size_t *k)
+uint32_t *arr_to_pairs(dyn_arr_t *arr, size_t *k)
 {
     size_t n = arr->last_index >= 256 ? arr->last_index - 255 : 0;
     uint32_t *pairs = malloc((n ? n : 1) * 2 * sizeof(uint32_t));
@@ -291,7 +289,7 @@ static uint32_t *arr_to_pairs(dyn_arr_t *arr, size_t *k)
 
 /* a multi-GB id buffer is first touched by the fetch's copy threads: ask for
  * transparent huge pages (512x fewer page faults where THP is in "madvise" mode) */
-static uint32_t *alloc_ids(size_t n)
+uint32_t *alloc_ids(size_t n)
 {
     const size_t bytes = (n ? n : 1) * sizeof(uint32_t);
     uint32_t *p = malloc(bytes);
