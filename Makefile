@@ -52,3 +52,13 @@ tests/asan/asan_host: tests/asan/asan_host.c tests/asan/gpu_stub.c $(CSRC) $(wil
 
 asan-host: tests/asan/asan_host
 .PHONY: asan-host
+
+# bpe_encode_split's host code (src/bpe_docs.c) the same way, against a host
+# model of the engine calls it makes (tests/asan_split/asan_split.c, a
+# stand-alone program); run by tests/test_asan_split.py
+tests/asan_split/asan_split: tests/asan_split/asan_split.c $(CSRC) $(CSRC_GPU) $(wildcard include/*.h $(PKG)/src/*.h)
+	$(CC) -O1 -g -std=c11 -D_GNU_SOURCE -fno-omit-frame-pointer -fsanitize=address,undefined \
+	    -fno-sanitize-recover=undefined -Iinclude -o $@ tests/asan_split/asan_split.c $(CSRC) $(CSRC_GPU) -lm -lpthread
+
+asan-split: tests/asan_split/asan_split
+.PHONY: asan-split

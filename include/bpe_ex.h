@@ -56,7 +56,17 @@ uint32_t *bpe_encode_docs(const uint8_t *bytes, size_t n, const uint64_t *doc_of
 char *bpe_decode_docs(const uint32_t *ids, size_t len, const uint64_t *id_off, size_t ndocs,
                       dyn_arr_t *pair_arr, int device, size_t *out_len, uint64_t **byte_off);
 
-/* statistics of the last compress/compress_ex/bpe_train_bytes/bpe_encode_bytes/bpe_encode_docs */
+/* Split bytes into pieces on the device by a two-table rule (cls[256], brk[16]:
+ * bpe_gpu.h, bpe_gpu_split / bpe_gpu_split_rule) and encode the pieces as
+ * documents, without the offsets passing through the host on the way.  *ndocs =
+ * pieces; *id_off and, unless byte_off is NULL, *byte_off (the piece starts
+ * followed by n) have *ndocs + 1 entries.  The caller frees the returned ids,
+ * *id_off and *byte_off with free(). */
+uint32_t *bpe_encode_split(const uint8_t *bytes, size_t n, const uint8_t *cls, const uint16_t *brk,
+                           dyn_arr_t *pair_arr, int device, size_t *len, uint64_t **id_off, uint64_t **byte_off,
+                           size_t *ndocs);
+
+/* statistics of the last compress/compress_ex/bpe_train_bytes/bpe_encode_bytes/bpe_encode_docs/bpe_encode_split */
 int bpe_last_stats(bpe_gpu_stats *out);
 
 /* compress / compress_ex / bpe_train_bytes / bpe_encode_bytes / decompress keep

@@ -242,6 +242,52 @@ int bpe_gpu_decode_docs(bpe_gpu_ctx *ctx, const uint32_t *ids, size_t len, const
 int bpe_gpu_docs_window(const uint64_t *doc_off, size_t ndocs, uint64_t n,
                         uint32_t core, uint32_t halo, uint64_t w, uint64_t *out8);
 
+/* ------------------------------------------------------------------------
+ * Splitting the loaded bytes into pieces on the device.  A rule is two tables:
+ * cls[256], the class (0..15) of every byte value, and brk[16]: bit c of brk[p]
+ * says that a piece starts at byte i when cls[b[i - 1]] == p and cls[b[i]] == c.
+ * Byte 0 always starts a piece.  The split's offsets are the piece starts in
+ * order followed by n: ndocs + 1 of them, no piece empty (n == 0: ndocs == 0 and
+ * the single offset 0).  They stay in HBM and are bpe_gpu_encode_docs' doc_off
+ * for bpe_gpu_encode_split: no host copy of them is made on the way.
+ *
+ * The presets are this project's own rules, NOT GPT-2's regular expression:
+ * no contractions, no look-ahead, no Unicode classes.
+ *   BPE_SPLIT_LINES  class 1 is '\n', the rest 0; brk[1] = 0x3: a piece ends
+ *                    after each newline and keeps it.
+ *   BPE_SPLIT_WORDS  class 1 letters A-Z a-z and every byte >= 0x80 (a UTF-8
+ *                    sequence never splits), 2 digits, 3 the space 0x20, 4 the
+ *                    other white space \t \n \v \f \r, 0 the rest.  A piece
+ *                    starts wherever the class changes, except that nothing
+ *                    starts after a space unless class 4 follows (spaces
+ *                    attach to what follows them): brk[p] = 0x1F & ~(1 << p)
+ *                    for p in 0, 1, 2, 4 and brk[3] = 1 << 4.
+ *
+ * The offsets belong to the loaded bytes.  bpe_gpu_load / _load_fd / _synth /
+ * _trim, bpe_gpu_train / _train_ex and a sharded group's load, synth and train
+ * on the context drop them; bpe_gpu_encode, _encode_docs, _encode_split and
+ * _decode keep them (several merge lists may be encoded over one split); a new
+ * bpe_gpu_split replaces them.  A call that needs them and finds none returns
+ * BPE_GPU_ESTATE.
+ * ---------------------------------------------------------------------- */
+enum { BPE_SPLIT_LINES = 0, BPE_SPLIT_WORDS = 1 };
+/* bytes one workgroup of the split kernels handles per step, and the largest grid
+   (a corpus of more than TILE * GRID bytes is walked in grid strides) */
+#define BPE_GPU_SPLIT_TILE 4096
+#define BPE_GPU_SPLIT_GRID 2048
+/* fill cls[256] / brk[16] with a preset (pure function, no GPU) */
+int bpe_gpu_split_rule(int preset, uint8_t *cls, uint16_t *brk);
+/* out4 = {BPE_GPU_SPLIT_TILE, BPE_GPU_SPLIT_TILE * BPE_GPU_SPLIT_GRID, 0, 0} (pure function, no GPU) */
+int bpe_gpu_split_info(uint64_t *out4);
+/* split the loaded bytes; *ndocs = pieces.  A cls entry above 15 is BPE_GPU_EINVAL. */
+int bpe_gpu_split(bpe_gpu_ctx *ctx, const uint8_t *cls, const uint16_t *brk, size_t *ndocs);
+/* the last split's offsets; out may be NULL, *count = ndocs + 1 */
+int bpe_gpu_fetch_split_offsets(bpe_gpu_ctx *ctx, uint64_t *out, size_t cap, size_t *count);
+/* bpe_gpu_encode_docs over the last split's offsets (resident: neither checked nor uploaded);
+   bpe_gpu_fetch_ids / _fetch_ids_range / _ids_checksum / _fetch_doc_offsets / _docs_info / _get_stats
+   serve what bpe_gpu_encode_docs leaves for the same offsets */
+int bpe_gpu_encode_split(bpe_gpu_ctx *ctx, const uint32_t *pairs, size_t n_merges);
+
 int bpe_gpu_get_stats(bpe_gpu_ctx *ctx, bpe_gpu_stats *st);
 
 /* Position-keyed checksum of the ids of the last train / encode, computed in

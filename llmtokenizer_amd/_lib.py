@@ -22,6 +22,7 @@ EXPORTS = [
     # bpe_ex.h
     "compress_ex", "bpe_train_bytes", "bpe_encode_bytes", "bpe_last_stats",
     "bpe_train_bytes_devices", "compress_multi", "bpe_release_engines", "bpe_encode_docs", "bpe_decode_docs",
+    "bpe_encode_split",
     # bpe_gpu.h
     "bpe_gpu_device_count", "bpe_gpu_create", "bpe_gpu_destroy", "bpe_gpu_load", "bpe_gpu_synth",
     "bpe_gpu_train", "bpe_gpu_fetch_merges", "bpe_gpu_fetch_ids", "bpe_gpu_encode", "bpe_gpu_decode",
@@ -39,6 +40,8 @@ EXPORTS = [
     # bpe_gpu.h: document batches
     "bpe_gpu_encode_docs", "bpe_gpu_fetch_doc_offsets", "bpe_gpu_docs_info", "bpe_gpu_decode_docs",
     "bpe_gpu_docs_window",
+    # bpe_gpu.h: splitting the resident bytes
+    "bpe_gpu_split_rule", "bpe_gpu_split_info", "bpe_gpu_split", "bpe_gpu_fetch_split_offsets", "bpe_gpu_encode_split",
 ]
 
 
@@ -186,6 +189,14 @@ def load():
     L.bpe_decode_docs.argtypes = [vp, sz, vp, sz, ctypes.POINTER(DynArr), ctypes.c_int, ctypes.POINTER(sz),
                                   ctypes.POINTER(u64p)]
     L.bpe_decode_docs.restype = ctypes.c_void_p
+    L.bpe_gpu_split_rule.argtypes = [ctypes.c_int, vp, vp]
+    L.bpe_gpu_split_info.argtypes = [vp]
+    L.bpe_gpu_split.argtypes = [vp, vp, vp, ctypes.POINTER(sz)]
+    L.bpe_gpu_fetch_split_offsets.argtypes = [vp, vp, sz, ctypes.POINTER(sz)]
+    L.bpe_gpu_encode_split.argtypes = [vp, vp, sz]
+    L.bpe_encode_split.argtypes = [vp, sz, vp, vp, ctypes.POINTER(DynArr), ctypes.c_int, ctypes.POINTER(sz),
+                                   ctypes.POINTER(u64p), ctypes.POINTER(u64p), ctypes.POINTER(sz)]
+    L.bpe_encode_split.restype = u32p
     L.bpe_release_engines.argtypes = []
     L.bpe_release_engines.restype = None
     _LIB = L

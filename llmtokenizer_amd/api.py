@@ -172,6 +172,68 @@ def encode_batch(docs, merges, device=0):
     return _take_ids(p, n.value), offsets
 
 
+SPLIT_PRESETS = {"lines": 0, "words": 1}  # bpe_gpu.h BPE_SPLIT_LINES / BPE_SPLIT_WORDS
+
+
+def split_rule(preset):
+    """The tables (cls uint8[256], brk uint16[16]) of a preset split rule, "lines"
+    or "words" (bpe_gpu.h bpe_gpu_split_rule; this project's rules, not GPT-2's
+    regular expression): a piece starts at byte i when bit cls[b[i]] of
+    brk[cls[b[i - 1]]] is set, and at byte 0."""
+    if preset not in SPLIT_PRESETS:
+        raise BpeError(f"split_rule: no preset {preset!r} (have {sorted(SPLIT_PRESETS)})")
+    L = _lib.load()
+    cls = np.zeros(256, dtype=np.uint8)
+    brk = np.zeros(16, dtype=np.uint16)
+    _lib.check(L.bpe_gpu_split_rule(SPLIT_PRESETS[preset], cls.ctypes.data_as(ctypes.c_void_p),
+                                    brk.ctypes.data_as(ctypes.c_void_p)), "split_rule")
+    return cls, brk
+
+
+def split_info():
+    """{"tile", "grid_bytes"}: bytes one workgroup of the split kernels handles per
+    step and bytes one grid step covers (bpe_gpu_split_info; for the tests)"""
+    out = np.zeros(4, dtype=np.uint64)
+    _lib.check(_lib.load().bpe_gpu_split_info(out.ctypes.data_as(ctypes.c_void_p)), "split_info")
+    return {"tile": int(out[0]), "grid_bytes": int(out[1])}
+
+
+def _rule_tables(rule):
+    cls, brk = split_rule(rule) if isinstance(rule, str) else rule
+    cls = np.ascontiguousarray(cls, dtype=np.uint8).reshape(-1)
+    brk = np.ascontiguousarray(brk, dtype=np.uint16).reshape(-1)
+    if cls.size != 256 or brk.size != 16:
+        raise BpeError("split rule: cls must hold 256 entries and brk 16")
+    return cls, brk
+
+
+def encode_split(data: bytes, merges, rule="words", device=0):
+    """Split data into pieces on the GPU (rule: a preset name or a (cls, brk)
+    pair, see split_rule) and encode the pieces as documents.  Returns (ids,
+    id_offsets, byte_offsets), both offsets uint64 of length pieces + 1: piece d
+    is data[byte_offsets[d]:byte_offsets[d + 1]] and its ids are
+    ids[id_offsets[d]:id_offsets[d + 1]] == encode(piece d, merges)."""
+    L = _lib.load()
+    cls, brk = _rule_tables(rule)
+    buf = np.frombuffer(data, dtype=np.uint8)
+    arr = _merges_to_arr(merges)
+    n, nd = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    ido, bo = ctypes.POINTER(ctypes.c_uint64)(), ctypes.POINTER(ctypes.c_uint64)()
+    vp = ctypes.c_void_p
+    try:
+        p = L.bpe_encode_split(buf.ctypes.data_as(vp), buf.size, cls.ctypes.data_as(vp), brk.ctypes.data_as(vp), arr,
+                               int(device), ctypes.byref(n), ctypes.byref(ido), ctypes.byref(bo), ctypes.byref(nd))
+    finally:
+        L.dyn_arr_free(arr)
+    if not p:
+        raise BpeError("bpe_encode_split failed")
+    id_off = np.ctypeslib.as_array(ido, shape=(nd.value + 1,)).copy()
+    byte_off = np.ctypeslib.as_array(bo, shape=(nd.value + 1,)).copy()
+    ctypes.CDLL(None).free(ctypes.cast(ido, vp))
+    ctypes.CDLL(None).free(ctypes.cast(bo, vp))
+    return _take_ids(p, n.value), id_off, byte_off
+
+
 def decode_batch(ids, offsets, merges, device=0):
     """Inverse of encode_batch: the list of the documents' bytes (NUL bytes dropped, as decompress does)."""
     L = _lib.load()
@@ -291,6 +353,31 @@ class Engine:
         m = np.ascontiguousarray(merges, dtype=np.uint32).reshape(-1)
         _lib.check(self.L.bpe_gpu_encode_docs(self.ctx, off.ctypes.data_as(ctypes.c_void_p), off.size - 1,
                                               m.ctypes.data_as(ctypes.c_void_p), m.size // 2), "encode_docs")
+
+    def split(self, rule="words"):
+        """split the resident bytes into pieces on the device (rule: a preset
+        name or a (cls, brk) pair, see split_rule); the offsets stay in HBM for
+        encode_split().  Returns the number of pieces."""
+        cls, brk = _rule_tables(rule)
+        nd = ctypes.c_size_t(0)
+        _lib.check(self.L.bpe_gpu_split(self.ctx, cls.ctypes.data_as(ctypes.c_void_p),
+                                        brk.ctypes.data_as(ctypes.c_void_p), ctypes.byref(nd)), "split")
+        return nd.value
+
+    def split_offsets(self):
+        """byte offsets of the last split (uint64: the piece starts followed by n)"""
+        n = ctypes.c_size_t(0)
+        _lib.check(self.L.bpe_gpu_fetch_split_offsets(self.ctx, None, 0, ctypes.byref(n)), "fetch_split_offsets")
+        out = np.zeros(n.value, dtype=np.uint64)
+        _lib.check(self.L.bpe_gpu_fetch_split_offsets(self.ctx, out.ctypes.data_as(ctypes.c_void_p), n.value,
+                                                      ctypes.byref(n)), "fetch_split_offsets")
+        return out
+
+    def encode_split(self, merges):
+        """encode_docs over the last split's resident offsets (bpe_gpu_encode_split);
+        then ids(), doc_offsets(), docs_info() as after encode_docs"""
+        m = np.ascontiguousarray(merges, dtype=np.uint32).reshape(-1)
+        _lib.check(self.L.bpe_gpu_encode_split(self.ctx, m.ctypes.data_as(ctypes.c_void_p), m.size // 2), "encode_split")
 
     def doc_offsets(self):
         """id offsets of the last encode_docs (uint64, ndocs + 1 entries)"""

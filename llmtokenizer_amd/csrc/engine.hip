@@ -26,6 +26,7 @@
 #include "encode.hip"
 #include "encode_win.hip"
 #include "encode_docs.hip"
+#include "split.hip"
 
 using namespace bpeamd;
 
@@ -295,6 +296,12 @@ struct bpe_gpu_ctx {
     uint64_t docs_n = 0;
     uint64_t *d_idoff = nullptr;
     uint64_t docs_info[8] = {};
+    // the last bpe_gpu_split: piece starts + n (device, [split_n + 1]).  A buffer of its own, outside
+    // train_allocs and the pool: it outlives the encodes over it and goes with the bytes it describes.
+    bool split_ready = false;
+    uint64_t split_n = 0;
+    uint64_t *d_split = nullptr;
+    size_t split_cap = 0;  // entries d_split holds
     size_t merges_done = 0;
     std::vector<std::pair<void *, size_t>> train_allocs;  // live buffers of the current run
     std::vector<std::pair<void *, size_t>> pool;          // released buffers, reused by size
@@ -326,9 +333,10 @@ struct bpe_gpu_ctx {
     // grow-only device scratch of decode (ids, pairs, elen, offsets, scan
     // temporaries, output, error words; slots 0-6), of the window encoder
     // (tables, halo bytes, rank exchange; 7-9), of bpe_gpu_decode_docs (id and byte offsets; 10-11),
+    // of bpe_gpu_split (start table, start masks, wave counts + their scan, scan temporaries; 12-15),
     // and the pinned staging of file loads
-    void *dscr[12] = {};
-    size_t dscr_cap[12] = {};
+    void *dscr[16] = {};
+    size_t dscr_cap[16] = {};
     std::vector<uint32_t> ew_stage;  // host image of the window encoder's tables (outlives the upload)
     uint8_t *stage[2] = {};
     hipEvent_t stage_ev[2] = {};
@@ -517,6 +525,7 @@ int setup_run(bpe_gpu_ctx *c, uint32_t mcap, bool encode) {
 
 int setup_run_body(bpe_gpu_ctx *c, uint32_t mcap, bool encode) {
     free_train(c);
+    if (!encode) c->split_ready = false;  // training: the split's offsets go (bpe_gpu.h)
     Eng &h = c->h;
     h.n0 = c->n0;
     h.mcap = mcap;
@@ -2322,18 +2331,20 @@ int ew_run(bpe_gpu_ctx *c, const EwPlan &P, const uint32_t *d_img, uint32_t halo
     return 0;
 }
 
-// Encode c's bytes as documents (h_off[ndocs + 1], validated) by windows
-// (encode_docs.hip) into c's ids and id offsets; *nfail = windows whose core
-// came out uncertain, wfail = their flags (filled when there are any).
-int ed_run(bpe_gpu_ctx *c, const EwPlan &P, const uint32_t *d_img, uint32_t halo, const uint64_t *h_off, uint64_t ndocs,
-           uint64_t *nfail, std::vector<uint32_t> &wfail) {
+// Encode c's bytes as documents (d_doc[ndocs + 1] on the device: uploaded and
+// validated by bpe_gpu_encode_docs, or a split's) by windows (encode_docs.hip)
+// into c's ids and id offsets; *nfail = windows whose core came out uncertain,
+// wfail = their flags (filled when there are any).  ms_upload: what the
+// caller's upload of the offsets took (BPE_EW_PROF's report).
+int ed_run(bpe_gpu_ctx *c, const EwPlan &P, const uint32_t *d_img, uint32_t halo, const uint64_t *d_doc, uint64_t ndocs,
+           uint64_t *nfail, std::vector<uint32_t> &wfail, double ms_upload) {
     const uint32_t core = EW_W - 2 * halo;
     const uint64_t n = c->n0, nwin = (n + core - 1) / core;
     int r;
     uint32_t *ids, *cnt, *wfirst, *rel, *d_wfail;
     uint16_t *stage;
     unsigned long long *off;
-    uint64_t *d_doc, *d_idoff;
+    uint64_t *d_idoff;
     if ((r = dalloc(c, &ids, std::max<uint64_t>(n, 1), false))) return r;
     if ((r = dalloc(c, &stage, std::max<uint64_t>(nwin * core, 1), false))) return r;
     if ((r = dalloc(c, &cnt, nwin + 4))) return r;  // zeroed: counts (+ a 0 after the last), ticket, failed windows
@@ -2341,15 +2352,9 @@ int ed_run(bpe_gpu_ctx *c, const EwPlan &P, const uint32_t *d_img, uint32_t halo
     if ((r = dalloc(c, &wfirst, nwin + 1, false))) return r;
     if ((r = dalloc(c, &d_wfail, std::max<uint64_t>(nwin, 1)))) return r;
     if ((r = dalloc(c, &rel, ndocs + 1))) return r;
-    if ((r = dalloc(c, &d_doc, ndocs + 1, false))) return r;
     if ((r = dalloc(c, &d_idoff, ndocs + 1, false))) return r;
     const bool prof = getenv_int("BPE_EW_PROF", 0) != 0;  // (then the phases below are synchronised and timed)
-    double tph[4] = {now_ms(), 0, 0, 0};
-    HIPCHK(hipMemcpyAsync(d_doc, h_off, (ndocs + 1) * 8, hipMemcpyHostToDevice, c->st));
-    if (prof) {
-        HIPCHK(hipStreamSynchronize(c->st));
-        tph[1] = now_ms();
-    }
+    double tph[4] = {0, now_ms(), 0, 0};
     c->h.ids_out = ids;
     c->d_idoff = d_idoff;
     EncDocArgs D{};
@@ -2408,7 +2413,7 @@ int ed_run(bpe_gpu_ctx *c, const EwPlan &P, const uint32_t *d_img, uint32_t halo
         const double wn = (double)std::max(1ull, h[5]);
         tph[3] = now_ms();
         fprintf(stderr, "enc_docs phases (ms): offsets upload %.2f, first documents + windows %.2f, scan + offsets + gather %.2f\n",
-                tph[1] - tph[0], tph[2] - tph[1], tph[3] - tph[2]);
+                ms_upload, tph[2] - tph[1], tph[3] - tph[2]);
         fprintf(stderr, "enc_docs: %llu windows, per window (us): init %.2f batches %.2f (merges %.2f, lookups %.2f) "
                 "output %.2f; batches with work %.1f of %u; lookup-list overflows %llu\n", h[5], h[0] / wn / 100.0,
                 h[1] / wn / 100.0, h[3] / wn / 100.0, h[7] / wn / 100.0, h[2] / wn / 100.0, h[4] / wn, P.nb, h[6]);
@@ -2502,6 +2507,7 @@ void bpe_gpu_destroy(bpe_gpu_ctx *c) {
         if (e) (void)hipEventDestroy(e);
     if (c->d_pres) hipFree(c->d_pres);
     if (c->d_enc_pairs) hipFree(c->d_enc_pairs);
+    if (c->d_split) hipFree(c->d_split);
     for (void *p : c->dscr)
         if (p) (void)hipFree(p);
     for (int k = 0; k < 2; k++) {
@@ -2527,6 +2533,7 @@ static int alloc_bytes(bpe_gpu_ctx *c, size_t n) {
     const bool same = c->n0 && n <= c->n0 + c->n0 / 8 && c->n0 <= n + n / 8;
     free_train(c, !same);
     c->pres_valid = false;
+    c->split_ready = false;  // the split's offsets describe the bytes replaced here
     if (!c->h.bytes || c->bytes_cap < n + 64) {  // (a buffer at least this large is kept)
         if (c->h.bytes) { (void)hipFree(c->h.bytes); c->h.bytes = nullptr; }
         HIPCHK(hipMalloc(&c->h.bytes, n + 64));
@@ -3163,7 +3170,11 @@ int bpe_gpu_trim(bpe_gpu_ctx *c) {
     c->n0 = 0;
     c->loaded = false;
     c->pres_valid = false;
-    for (int k = 0; k < 12; k++) {
+    c->split_ready = false;
+    if (c->d_split) (void)hipFree(c->d_split);
+    c->d_split = nullptr;
+    c->split_cap = 0;
+    for (int k = 0; k < 16; k++) {
         if (c->dscr[k]) (void)hipFree(c->dscr[k]);
         c->dscr[k] = nullptr;
         c->dscr_cap[k] = 0;
@@ -3214,18 +3225,24 @@ int bpe_gpu_docs_window(const uint64_t *doc_off, size_t ndocs, uint64_t n, uint3
     return 0;
 }
 
-int bpe_gpu_encode_docs(bpe_gpu_ctx *c, const uint64_t *doc_off, size_t ndocs, const uint32_t *pairs, size_t n_merges) {
-    if (!c || !doc_off || (!pairs && n_merges)) return BPE_GPU_EINVAL;
-    if (!c->loaded) return fail(BPE_GPU_ESTATE, "encode before load");
-    if (n_merges > 0xFFFFFEFFull) return fail(BPE_GPU_ERANGE, "merge list too long");
+}  // extern "C"
+
+// bpe_gpu_encode_docs after its checks (doc_off: the caller's host offsets,
+// t_chk: when their check began) and bpe_gpu_encode_split (doc_off == nullptr:
+// the offsets are the split's, resident in c->d_split; the cold paths below
+// that read offsets on the host download them, and only they do).
+static int encode_docs_run(bpe_gpu_ctx *c, const uint64_t *doc_off, size_t ndocs, const uint32_t *pairs, size_t n_merges,
+                           double t_chk) {
     const uint64_t n = c->n0;
-    const double t_chk = now_ms();
-    if (ndocs > 0xFFFFFFFEull) return fail(BPE_GPU_EINVAL, "encode_docs: more than 2^32-2 documents");
-    if (doc_off[0] != 0) return fail(BPE_GPU_EINVAL, "encode_docs: the first offset is not 0");
-    if (doc_off[ndocs] != n) return fail(BPE_GPU_EINVAL, "encode_docs: the last offset is not the number of loaded bytes");
-    bool dec = false;  // (a reduction, not an early exit: 10^7 offsets are checked at memory speed)
-    for (size_t d = 0; d < ndocs; d++) dec |= doc_off[d] > doc_off[d + 1];
-    if (dec) return fail(BPE_GPU_EINVAL, "encode_docs: offsets decrease");
+    const bool resident = doc_off == nullptr;
+    std::vector<uint64_t> h_split;
+    auto host_offsets = [&]() -> int {
+        if (doc_off) return 0;
+        h_split.resize(ndocs + 1);
+        const int e = d2h_staged(c, h_split.data(), c->d_split, (ndocs + 1) * 8);
+        if (!e) doc_off = h_split.data();
+        return e;
+    };
     HIPCHK(hipSetDevice(c->dev));
     c->stats = bpe_gpu_stats{};
     c->stats.n_in = n;
@@ -3250,8 +3267,22 @@ int bpe_gpu_encode_docs(bpe_gpu_ctx *c, const uint64_t *doc_off, size_t ndocs, c
         core = EW_W - 2 * halo;
         nwin = (n + core - 1) / core;
         std::vector<uint32_t> wfail;
-        if ((r = ed_run(c, P, (const uint32_t *)d_img, (uint32_t)halo, doc_off, ndocs, &wfailed, wfail))) return r;
+        const uint64_t *d_doc = c->d_split;
+        double ms_upload = 0;
+        if (!resident) {
+            const double tu = now_ms();
+            uint64_t *up;
+            if ((r = dalloc(c, &up, ndocs + 1, false))) return r;
+            HIPCHK(hipMemcpyAsync(up, doc_off, (ndocs + 1) * 8, hipMemcpyHostToDevice, c->st));
+            if (getenv_int("BPE_EW_PROF", 0)) {
+                HIPCHK(hipStreamSynchronize(c->st));
+                ms_upload = now_ms() - tu;
+            }
+            d_doc = up;
+        }
+        if ((r = ed_run(c, P, (const uint32_t *)d_img, (uint32_t)halo, d_doc, ndocs, &wfailed, wfail, ms_upload))) return r;
         first_pass = true;
+        if (wfailed && (r = host_offsets())) return r;
         if (wfailed) failed.assign(ndocs, 0);
         if (wfailed)  // a document fails with any window holding one of its bytes in its core
             for (size_t d = 0; d < ndocs; d++) {
@@ -3261,6 +3292,7 @@ int bpe_gpu_encode_docs(bpe_gpu_ctx *c, const uint64_t *doc_off, size_t ndocs, c
             }
     } else {
         // no plan (too many merges or layers), or no bytes: every document with bytes goes through the fallback
+        if ((r = host_offsets())) return r;
         failed.assign(ndocs, 0);
         for (size_t d = 0; d < ndocs; d++) nfailed += failed[d] = doc_off[d] != doc_off[d + 1];
     }
@@ -3330,6 +3362,136 @@ int bpe_gpu_encode_docs(bpe_gpu_ctx *c, const uint64_t *doc_off, size_t ndocs, c
     c->stats.ms_train = t1 - t0;
     c->stats.ms_total = t1 - t0;
     return 0;
+}
+
+extern "C" {
+
+int bpe_gpu_encode_docs(bpe_gpu_ctx *c, const uint64_t *doc_off, size_t ndocs, const uint32_t *pairs, size_t n_merges) {
+    if (!c || !doc_off || (!pairs && n_merges)) return BPE_GPU_EINVAL;
+    if (!c->loaded) return fail(BPE_GPU_ESTATE, "encode before load");
+    if (n_merges > 0xFFFFFEFFull) return fail(BPE_GPU_ERANGE, "merge list too long");
+    const uint64_t n = c->n0;
+    const double t_chk = now_ms();
+    if (ndocs > 0xFFFFFFFEull) return fail(BPE_GPU_EINVAL, "encode_docs: more than 2^32-2 documents");
+    if (doc_off[0] != 0) return fail(BPE_GPU_EINVAL, "encode_docs: the first offset is not 0");
+    if (doc_off[ndocs] != n) return fail(BPE_GPU_EINVAL, "encode_docs: the last offset is not the number of loaded bytes");
+    bool dec = false;  // (a reduction, not an early exit: 10^7 offsets are checked at memory speed)
+    for (size_t d = 0; d < ndocs; d++) dec |= doc_off[d] > doc_off[d + 1];
+    if (dec) return fail(BPE_GPU_EINVAL, "encode_docs: offsets decrease");
+    return encode_docs_run(c, doc_off, ndocs, pairs, n_merges, t_chk);
+}
+
+// ------------------------------------------------ pieces of the resident bytes (split.hip)
+
+int bpe_gpu_split_rule(int preset, uint8_t *cls, uint16_t *brk) {
+    if (!cls || !brk) return fail(BPE_GPU_EINVAL, "split_rule: bad argument");
+    memset(cls, 0, 256);
+    memset(brk, 0, 16 * sizeof(uint16_t));
+    if (preset == BPE_SPLIT_LINES) {
+        cls['\n'] = 1;
+        brk[1] = 0x3;
+        return 0;
+    }
+    if (preset != BPE_SPLIT_WORDS) return fail(BPE_GPU_EINVAL, "split_rule: no such preset");
+    for (int b = 0; b < 256; b++)
+        cls[b] = (b >= 'A' && b <= 'Z') || (b >= 'a' && b <= 'z') || b >= 0x80 ? 1
+                 : b >= '0' && b <= '9'                                        ? 2
+                 : b == ' '                                                    ? 3
+                 : b >= '\t' && b <= '\r'                                      ? 4
+                                                                               : 0;
+    for (int p = 0; p < 5; p++) brk[p] = (uint16_t)(0x1F & ~(1 << p));
+    brk[3] = 1 << 4;
+    return 0;
+}
+
+int bpe_gpu_split_info(uint64_t *out4) {
+    if (!out4) return BPE_GPU_EINVAL;
+    out4[0] = SP_TILE;
+    out4[1] = (uint64_t)SP_TILE * SP_GRID;
+    out4[2] = out4[3] = 0;
+    return 0;
+}
+
+int bpe_gpu_split(bpe_gpu_ctx *c, const uint8_t *cls, const uint16_t *brk, size_t *ndocs) {
+    if (!c || !cls || !brk || !ndocs) return BPE_GPU_EINVAL;
+    if (!c->loaded) return fail(BPE_GPU_ESTATE, "split before load");
+    SplitRule R;
+    for (int b = 0; b < 256; b++)
+        if ((R.cls[b] = cls[b]) > 15) return fail(BPE_GPU_EINVAL, "split: a class above 15");
+    memcpy(R.brk, brk, sizeof R.brk);
+    HIPCHK(hipSetDevice(c->dev));
+    c->split_ready = false;
+    const uint64_t n = c->n0, ntiles = (n + SP_TILE - 1) / SP_TILE, nwt = ntiles * (SP_T / 64);
+    unsigned long long total = 0;
+    uint16_t *mask = nullptr;
+    unsigned long long *woff = nullptr;
+    int r;
+    if (n) {
+        void *tbl, *pm, *pc, *tmp;
+        // counts [nwt + 1] (the last one 0) and their scan [nwt + 1] in one slot
+        if ((r = dscratch(c, 12, SP_TBL * 4, &tbl)) || (r = dscratch(c, 13, ntiles * SP_T * 2, &pm)) ||
+            (r = dscratch(c, 14, (nwt + 1) * 8 + ((nwt + 1) * 4 + 7) / 8 * 8, &pc)))
+            return r;
+        mask = (uint16_t *)pm;
+        woff = (unsigned long long *)pc;
+        uint32_t *wcnt = (uint32_t *)(woff + nwt + 1);
+        const uint32_t grid = (uint32_t)std::min<uint64_t>(ntiles, SP_GRID);
+        HIPCHK(hipMemsetAsync(wcnt + nwt, 0, 4, c->st));
+        k_split_table<<<SP_TBL / SP_T, SP_T, 0, c->st>>>(R, (uint32_t *)tbl);
+        HIPCHK(hipGetLastError());
+        k_split_mark<<<grid, SP_T, 0, c->st>>>(c->h.bytes, n, (const uint32_t *)tbl, ntiles, mask, wcnt);
+        HIPCHK(hipGetLastError());
+        size_t tb = 0;
+        HIPCHK(rocprim::exclusive_scan(nullptr, tb, wcnt, woff, 0ull, nwt + 1, rocprim::plus<unsigned long long>(), c->st));
+        if ((r = dscratch(c, 15, tb, &tmp))) return r;
+        HIPCHK(rocprim::exclusive_scan(tmp, tb, wcnt, woff, 0ull, nwt + 1, rocprim::plus<unsigned long long>(), c->st));
+        HIPCHK(hipMemcpyAsync(&total, woff + nwt, 8, hipMemcpyDeviceToHost, c->st));
+        HIPCHK(hipStreamSynchronize(c->st));
+        if (total == 0 || total > n) return fail(BPE_GPU_EINTERNAL, "split: piece count out of range");
+    }
+    if (c->split_cap < total + 1) {
+        HIPCHK(hipStreamSynchronize(c->st));
+        if (c->d_split) (void)hipFree(c->d_split);
+        c->d_split = nullptr;
+        c->split_cap = 0;
+        const size_t cap = std::max<size_t>(total + 1, 32);
+        hipError_t e = hipMalloc(&c->d_split, cap * 8);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(BPE_GPU_ENOMEM, "split: hipMalloc of the offsets", e);
+        }
+        c->split_cap = cap;
+    }
+    if (n) {
+        const uint32_t grid = (uint32_t)std::min<uint64_t>(ntiles, SP_GRID);
+        k_split_emit<<<grid, SP_T, 0, c->st>>>(mask, woff, ntiles, n, c->d_split);
+        HIPCHK(hipGetLastError());
+    } else {
+        HIPCHK(hipMemsetAsync(c->d_split, 0, 8, c->st));
+    }
+    HIPCHK(hipStreamSynchronize(c->st));
+    c->split_n = total;
+    c->split_ready = true;
+    *ndocs = (size_t)total;
+    return 0;
+}
+
+int bpe_gpu_fetch_split_offsets(bpe_gpu_ctx *c, uint64_t *out, size_t cap, size_t *count) {
+    if (!c || !count) return BPE_GPU_EINVAL;
+    if (!c->loaded || !c->split_ready) return fail(BPE_GPU_ESTATE, "no split offsets: split first");
+    HIPCHK(hipSetDevice(c->dev));
+    *count = c->split_n + 1;
+    const size_t k = out ? std::min<size_t>(cap, c->split_n + 1) : 0;
+    if (k) return d2h_staged(c, out, c->d_split, k * 8);
+    return 0;
+}
+
+int bpe_gpu_encode_split(bpe_gpu_ctx *c, const uint32_t *pairs, size_t n_merges) {
+    if (!c || (!pairs && n_merges)) return BPE_GPU_EINVAL;
+    if (!c->loaded) return fail(BPE_GPU_ESTATE, "encode before load");
+    if (!c->split_ready) return fail(BPE_GPU_ESTATE, "encode_split: no split of the loaded bytes");
+    if (n_merges > 0xFFFFFEFFull) return fail(BPE_GPU_ERANGE, "merge list too long");
+    return encode_docs_run(c, nullptr, c->split_n, pairs, n_merges, now_ms());
 }
 
 int bpe_gpu_fetch_doc_offsets(bpe_gpu_ctx *c, uint64_t *out, size_t cap, size_t *count) {

@@ -1,6 +1,7 @@
 /*
  * bpe_docs.c -- document batches of bpe_ex.h: bpe_encode_docs / bpe_decode_docs
- * over the engine's bpe_gpu_encode_docs / bpe_gpu_decode_docs, on the cached
+ * over the engine's bpe_gpu_encode_docs / bpe_gpu_decode_docs, and
+ * bpe_encode_split over bpe_gpu_split / bpe_gpu_encode_split, on the cached
  * engine contexts of bpe.c.
  */
 #include "bpe_internal.h"
@@ -38,6 +39,49 @@ done:
     }
     *len = n_ids;
     *id_off = offs;
+    return ids;
+}
+
+uint32_t *bpe_encode_split(const uint8_t *bytes, size_t n, const uint8_t *cls, const uint16_t *brk, dyn_arr_t *pair_arr,
+                           int device, size_t *len, uint64_t **id_off, uint64_t **byte_off, size_t *ndocs)
+{
+    if ((!bytes && n) || !cls || !brk || !pair_arr || !len || !id_off || !ndocs) return NULL;
+    bpe_gpu_ctx *ctx = NULL;
+    size_t k = 0, n_ids = 0, n_off = 0, pieces = 0;
+    uint32_t *pairs = arr_to_pairs(pair_arr, &k), *ids = NULL;
+    uint64_t *offs = NULL, *boffs = NULL;
+    int rc, ok = 0;
+    if (!pairs) return NULL;
+    if ((rc = open_engine(device, &ctx))) goto done;
+    if ((rc = bpe_gpu_load(ctx, bytes, n))) { report("load", rc); goto done; }
+    if ((rc = bpe_gpu_split(ctx, cls, brk, &pieces))) { report("split", rc); goto done; }
+    if ((rc = bpe_gpu_encode_split(ctx, pairs, k))) { report("encode split", rc); goto done; }
+    if ((rc = bpe_gpu_fetch_ids(ctx, NULL, 0, &n_ids))) { report("fetch ids", rc); goto done; }
+    ids = alloc_ids(n_ids);
+    offs = malloc((pieces + 1) * sizeof(uint64_t));
+    if (byte_off) boffs = malloc((pieces + 1) * sizeof(uint64_t));
+    if (!ids || !offs || (byte_off && !boffs)) goto done;
+    if ((rc = bpe_gpu_fetch_ids(ctx, ids, n_ids, &n_ids))) { report("fetch ids", rc); goto done; }
+    if ((rc = bpe_gpu_fetch_doc_offsets(ctx, offs, pieces + 1, &n_off))) { report("fetch doc offsets", rc); goto done; }
+    if (boffs && (rc = bpe_gpu_fetch_split_offsets(ctx, boffs, pieces + 1, &n_off))) {
+        report("fetch split offsets", rc);
+        goto done;
+    }
+    bpe_gpu_get_stats(ctx, &g_last_stats);
+    ok = 1;
+done:
+    close_engine(device, ctx, ok);
+    free(pairs);
+    if (!ok) {
+        free(ids);
+        free(offs);
+        free(boffs);
+        return NULL;
+    }
+    *len = n_ids;
+    *id_off = offs;
+    if (byte_off) *byte_off = boffs;
+    *ndocs = pieces;
     return ids;
 }
 
