@@ -16,6 +16,10 @@ COBJ := $(patsubst $(PKG)/src/%.c,$(BUILD)/%.o,$(CSRC))
 # host code over engine calls that tests/asan/gpu_stub.c does not stub: in the library, not in CSRC
 CSRC_GPU := $(PKG)/src/bpe_docs.c
 COBJ_GPU := $(patsubst $(PKG)/src/%.c,$(BUILD)/%.o,$(CSRC_GPU))
+# host code over bpe_gpu_train_split & co., which the host model of tests/asan_split does not have either:
+# a list of its own (tests/asan_train_split has the model for it)
+CSRC_TS := $(PKG)/src/bpe_train_split.c
+COBJ_TS := $(patsubst $(PKG)/src/%.c,$(BUILD)/%.o,$(CSRC_TS))
 HIPDEPS := $(wildcard $(PKG)/csrc/*.hip $(PKG)/csrc/*.h) include/bpe_gpu.h
 
 all: $(PKG)/libbpe_amd.so tools/bpe_main oracle
@@ -29,7 +33,7 @@ $(BUILD)/engine.o: $(HIPDEPS) | $(BUILD)
 $(BUILD)/%.o: $(PKG)/src/%.c $(wildcard include/*.h $(PKG)/src/*.h) | $(BUILD)
 	$(CC) $(CFLAGS) -c $< -o $@
 
-$(PKG)/libbpe_amd.so: $(BUILD)/engine.o $(COBJ) $(COBJ_GPU)
+$(PKG)/libbpe_amd.so: $(BUILD)/engine.o $(COBJ) $(COBJ_GPU) $(COBJ_TS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -lm -ldl -lpthread
 
 tools/bpe_main: tools/bpe_main.c $(PKG)/libbpe_amd.so
@@ -62,3 +66,13 @@ tests/asan_split/asan_split: tests/asan_split/asan_split.c $(CSRC) $(CSRC_GPU) $
 
 asan-split: tests/asan_split/asan_split
 .PHONY: asan-split
+
+# bpe_train_split's host code (src/bpe_train_split.c) the same way, against a host
+# model of the engine calls it makes (tests/asan_train_split/asan_train_split.c);
+# run by tests/test_asan_train_split.py
+tests/asan_train_split/asan_train_split: tests/asan_train_split/asan_train_split.c $(CSRC) $(CSRC_TS) $(wildcard include/*.h $(PKG)/src/*.h)
+	$(CC) -O1 -g -std=c11 -D_GNU_SOURCE -fno-omit-frame-pointer -fsanitize=address,undefined \
+	    -fno-sanitize-recover=undefined -Iinclude -o $@ tests/asan_train_split/asan_train_split.c $(CSRC) $(CSRC_TS) -lm -lpthread
+
+asan-train-split: tests/asan_train_split/asan_train_split
+.PHONY: asan-train-split

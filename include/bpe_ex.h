@@ -66,6 +66,14 @@ uint32_t *bpe_encode_split(const uint8_t *bytes, size_t n, const uint8_t *cls, c
                            dyn_arr_t *pair_arr, int device, size_t *len, uint64_t **id_off, uint64_t **byte_off,
                            size_t *ndocs);
 
+/* Split bytes into pieces on the device by the same two-table rule and train on
+ * the pieces (bpe_gpu.h, bpe_gpu_train_split): the merges never cross a piece
+ * boundary, so bpe_encode_split with the same rule can apply every one of them.
+ * max_merges < 0: until the stop rule.  Returns the merge list in the shape
+ * compress() returns it (the caller frees it with dyn_arr_free()), NULL on failure. */
+dyn_arr_t *bpe_train_split(const uint8_t *bytes, size_t n, const uint8_t *cls, const uint16_t *brk, long max_merges,
+                           int device);
+
 /* statistics of the last compress/compress_ex/bpe_train_bytes/bpe_encode_bytes/bpe_encode_docs/bpe_encode_split */
 int bpe_last_stats(bpe_gpu_stats *out);
 

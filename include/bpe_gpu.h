@@ -288,6 +288,39 @@ int bpe_gpu_fetch_split_offsets(bpe_gpu_ctx *ctx, uint64_t *out, size_t cap, siz
    serve what bpe_gpu_encode_docs leaves for the same offsets */
 int bpe_gpu_encode_split(bpe_gpu_ctx *ctx, const uint32_t *pairs, size_t n_merges);
 
+/* ------------------------------------------------------------------------
+ * Training on the pieces of the last split: merges that never cross a piece
+ * boundary, the list bpe_gpu_encode_split can apply in full.
+ *
+ * The corpus is the multiset of pieces, each its bytes as ids 0..255.
+ * count(a, b) is the number of positions, over all pieces, where a is followed
+ * by b inside one piece.  Merge r takes the pair with the largest count, ties to
+ * the smaller a and then the smaller b, gives it the id 256 + r and applies it
+ * inside every piece from left to right (a run a a a under (a, a) becomes z a; a
+ * run ends with its piece).  Training stops when no pair is left or the largest
+ * count is <= 1 (stop_reason 1, checked first), when max_merges merges are made
+ * (2; max_merges < 0: no cap of the caller's), or at the engine's own cap (3), as
+ * bpe_gpu_stats.stop_reason counts them.  The resident bytes, the split's
+ * offsets and the ids of an earlier encode stay as they are.
+ *
+ * The results (merges, the info fields, the piece table) belong to the split's
+ * offsets and go with them: whatever drops those (above) drops these, and so
+ * does a new bpe_gpu_split.  A call that needs them and finds none returns
+ * BPE_GPU_ESTATE.
+ * ---------------------------------------------------------------------- */
+/* BPE_GPU_ESTATE before a load or without a split of the loaded bytes */
+int bpe_gpu_train_split(bpe_gpu_ctx *ctx, long max_merges, size_t *n_merges);
+/* the merges of the last bpe_gpu_train_split as (a, b) pairs; out may be NULL, *count = merges */
+int bpe_gpu_fetch_split_merges(bpe_gpu_ctx *ctx, uint32_t *out, size_t cap, size_t *count);
+/* out8 = {pieces, entries (distinct pieces; one per piece longer than the next-to-last field), bytes of the
+   entries, pieces longer than that, merges, stop_reason, the longest piece that is deduplicated, slots of
+   the piece table} */
+int bpe_gpu_train_split_info(bpe_gpu_ctx *ctx, uint64_t *out8);
+/* the entries in start order: the start of the first piece with these bytes, their length and how many
+   pieces hold them; any of the three arrays may be NULL, *entries = their number */
+int bpe_gpu_fetch_piece_table(bpe_gpu_ctx *ctx, uint64_t *start, uint32_t *len, uint32_t *count, size_t cap,
+                              size_t *entries);
+
 int bpe_gpu_get_stats(bpe_gpu_ctx *ctx, bpe_gpu_stats *st);
 
 /* Position-keyed checksum of the ids of the last train / encode, computed in

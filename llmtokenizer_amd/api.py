@@ -234,6 +234,25 @@ def encode_split(data: bytes, merges, rule="words", device=0):
     return _take_ids(p, n.value), id_off, byte_off
 
 
+def train_split(data: bytes, rule="words", max_merges=-1, device=0):
+    """Split data into pieces on the GPU (rule as in encode_split) and train on the
+    pieces: merges that never cross a piece boundary, so encode_split with the same
+    rule can apply every one of them (bpe_ex.h bpe_train_split).  Returns the
+    merges, (k, 2) uint32 for ids 256..255+k."""
+    L = _lib.load()
+    cls, brk = _rule_tables(rule)
+    buf = np.frombuffer(data, dtype=np.uint8)
+    vp = ctypes.c_void_p
+    arr = L.bpe_train_split(buf.ctypes.data_as(vp), buf.size, cls.ctypes.data_as(vp), brk.ctypes.data_as(vp),
+                            int(max_merges), int(device))
+    if not arr:
+        raise BpeError("bpe_train_split failed")
+    try:
+        return _arr_to_merges(arr)
+    finally:
+        L.dyn_arr_free(arr)
+
+
 def decode_batch(ids, offsets, merges, device=0):
     """Inverse of encode_batch: the list of the documents' bytes (NUL bytes dropped, as decompress does)."""
     L = _lib.load()
@@ -378,6 +397,45 @@ class Engine:
         then ids(), doc_offsets(), docs_info() as after encode_docs"""
         m = np.ascontiguousarray(merges, dtype=np.uint32).reshape(-1)
         _lib.check(self.L.bpe_gpu_encode_split(self.ctx, m.ctypes.data_as(ctypes.c_void_p), m.size // 2), "encode_split")
+
+    def train_split(self, max_merges=-1):
+        """train on the pieces of the last split (bpe_gpu_train_split): the bytes, the
+        offsets and earlier ids stay; then split_merges(), train_split_info(), piece_table().
+        Returns the number of merges."""
+        k = ctypes.c_size_t(0)
+        _lib.check(self.L.bpe_gpu_train_split(self.ctx, int(max_merges), ctypes.byref(k)), "train_split")
+        return k.value
+
+    def split_merges(self):
+        """the merges of the last train_split, (k, 2) uint32"""
+        cnt = ctypes.c_size_t(0)
+        _lib.check(self.L.bpe_gpu_fetch_split_merges(self.ctx, None, 0, ctypes.byref(cnt)), "fetch_split_merges")
+        out = np.zeros(2 * max(cnt.value, 1), dtype=np.uint32)
+        _lib.check(self.L.bpe_gpu_fetch_split_merges(self.ctx, out.ctypes.data_as(ctypes.c_void_p), cnt.value,
+                                                     ctypes.byref(cnt)), "fetch_split_merges")
+        return out[: 2 * cnt.value].reshape(-1, 2)
+
+    TRAIN_SPLIT_INFO = ("pieces", "entries", "entry_bytes", "long_pieces", "merges", "stop_reason", "dedup_max",
+                        "table_slots")
+
+    def train_split_info(self):
+        """counters of the last train_split (bpe_gpu_train_split_info)"""
+        out = np.zeros(8, dtype=np.uint64)
+        _lib.check(self.L.bpe_gpu_train_split_info(self.ctx, out.ctypes.data_as(ctypes.c_void_p)), "train_split_info")
+        return {k: int(out[i]) for i, k in enumerate(self.TRAIN_SPLIT_INFO)}
+
+    def piece_table(self):
+        """the distinct pieces of the last train_split in start order: (start uint64,
+        length uint32, count uint32); a piece longer than dedup_max is an entry of its own"""
+        n = ctypes.c_size_t(0)
+        _lib.check(self.L.bpe_gpu_fetch_piece_table(self.ctx, None, None, None, 0, ctypes.byref(n)), "fetch_piece_table")
+        st = np.zeros(max(n.value, 1), dtype=np.uint64)
+        ln = np.zeros(max(n.value, 1), dtype=np.uint32)
+        ct = np.zeros(max(n.value, 1), dtype=np.uint32)
+        vp = ctypes.c_void_p
+        _lib.check(self.L.bpe_gpu_fetch_piece_table(self.ctx, st.ctypes.data_as(vp), ln.ctypes.data_as(vp),
+                                                    ct.ctypes.data_as(vp), n.value, ctypes.byref(n)), "fetch_piece_table")
+        return st[: n.value], ln[: n.value], ct[: n.value]
 
     def doc_offsets(self):
         """id offsets of the last encode_docs (uint64, ndocs + 1 entries)"""

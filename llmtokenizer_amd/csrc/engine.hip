@@ -27,6 +27,7 @@
 #include "encode_win.hip"
 #include "encode_docs.hip"
 #include "split.hip"
+#include "train_split.hip"
 
 using namespace bpeamd;
 
@@ -302,6 +303,11 @@ struct bpe_gpu_ctx {
     uint64_t split_n = 0;
     uint64_t *d_split = nullptr;
     size_t split_cap = 0;  // entries d_split holds
+    // the last bpe_gpu_train_split over those offsets: its merges (host), bpe_gpu_train_split_info's fields and
+    // the piece table (scratch slots 22-24).  Valid while split_ready: whatever drops the offsets drops these.
+    bool ts_ready = false;
+    std::vector<uint32_t> ts_merges;
+    uint64_t ts_info[8] = {};
     size_t merges_done = 0;
     std::vector<std::pair<void *, size_t>> train_allocs;  // live buffers of the current run
     std::vector<std::pair<void *, size_t>> pool;          // released buffers, reused by size
@@ -334,9 +340,11 @@ struct bpe_gpu_ctx {
     // temporaries, output, error words; slots 0-6), of the window encoder
     // (tables, halo bytes, rank exchange; 7-9), of bpe_gpu_decode_docs (id and byte offsets; 10-11),
     // of bpe_gpu_split (start table, start masks, wave counts + their scan, scan temporaries; 12-15),
+    // of bpe_gpu_train_split (piece table 16-17, control words 18, entry records 19-25, scan and sort
+    // temporaries 26, tokens and their entries 27-30, rewrite flags and scans 31-34, pair table 35-37),
     // and the pinned staging of file loads
-    void *dscr[16] = {};
-    size_t dscr_cap[16] = {};
+    void *dscr[38] = {};
+    size_t dscr_cap[38] = {};
     std::vector<uint32_t> ew_stage;  // host image of the window encoder's tables (outlives the upload)
     uint8_t *stage[2] = {};
     hipEvent_t stage_ev[2] = {};
@@ -3174,7 +3182,7 @@ int bpe_gpu_trim(bpe_gpu_ctx *c) {
     if (c->d_split) (void)hipFree(c->d_split);
     c->d_split = nullptr;
     c->split_cap = 0;
-    for (int k = 0; k < 16; k++) {
+    for (int k = 0; k < (int)(sizeof c->dscr / sizeof c->dscr[0]); k++) {
         if (c->dscr[k]) (void)hipFree(c->dscr[k]);
         c->dscr[k] = nullptr;
         c->dscr_cap[k] = 0;
@@ -3421,6 +3429,7 @@ int bpe_gpu_split(bpe_gpu_ctx *c, const uint8_t *cls, const uint16_t *brk, size_
     memcpy(R.brk, brk, sizeof R.brk);
     HIPCHK(hipSetDevice(c->dev));
     c->split_ready = false;
+    c->ts_ready = false;  // bpe_gpu_train_split's results describe the offsets replaced here
     const uint64_t n = c->n0, ntiles = (n + SP_TILE - 1) / SP_TILE, nwt = ntiles * (SP_T / 64);
     unsigned long long total = 0;
     uint16_t *mask = nullptr;
@@ -3492,6 +3501,224 @@ int bpe_gpu_encode_split(bpe_gpu_ctx *c, const uint32_t *pairs, size_t n_merges)
     if (!c->split_ready) return fail(BPE_GPU_ESTATE, "encode_split: no split of the loaded bytes");
     if (n_merges > 0xFFFFFEFFull) return fail(BPE_GPU_ERANGE, "merge list too long");
     return encode_docs_run(c, nullptr, c->split_n, pairs, n_merges, now_ms());
+}
+
+// ------------------------------------------------ training on the pieces (train_split.hip)
+
+// workgroups for `items` elements at `per` of them per thread, TS_GRID at most (the kernels stride)
+static uint32_t ts_grid(uint64_t items, uint32_t per = 1) {
+    const uint64_t chunk = (uint64_t)TS_T * per;
+    return (uint32_t)std::min<uint64_t>(std::max<uint64_t>((items + chunk - 1) / chunk, 1), TS_GRID);
+}
+
+// the control words on the host (one synchronisation)
+static int ts_read_ctl(bpe_gpu_ctx *c, const uint32_t *ctl, uint32_t *hc) {
+    HIPCHK(hipMemcpyAsync(hc, ctl, 16 * 4, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipStreamSynchronize(c->st));
+    return 0;
+}
+
+// Stage A: the pieces as weighted entries in start order.  Leaves the piece indices and counts in scratch
+// slots 21 / 22, starts and lengths in 23 / 24, the scanned lengths in 25; *E entries, *T bytes of entries.
+static int ts_piece_table(bpe_gpu_ctx *c, uint32_t *ctl, uint64_t *E, uint64_t *T, uint64_t *nlong, uint64_t *slots) {
+    const uint64_t P = c->split_n;
+    const uint64_t *off = c->d_split;
+    uint32_t hc[16];
+    int r;
+    // the table starts small (text has few distinct pieces) and grows fourfold when a probe chain runs out;
+    // at 2 P slots or more a chain of TS_PROBE is a defect of the hash, not load
+    const uint64_t smax = std::max<uint64_t>(pow2_at_least(2 * P), 1024) * 16;
+    const int knob = getenv_int("BPE_TS_SLOTS", 0);
+    uint64_t S = knob > 0 ? pow2_at_least(std::max(knob, 64)) : std::min<uint64_t>(std::max<uint64_t>(pow2_at_least(2 * P), 1024), 1u << 22);
+    void *pslot, *pcnt;
+    for (;;) {
+        if ((r = dscratch(c, 16, S * 8, &pslot)) || (r = dscratch(c, 17, S * 4, &pcnt))) return r;
+        HIPCHK(hipMemsetAsync(pslot, 0xFF, S * 8, c->st));
+        HIPCHK(hipMemsetAsync(pcnt, 0, S * 4, c->st));
+        HIPCHK(hipMemsetAsync(ctl, 0, 16 * 4, c->st));
+        k_ts_insert<<<ts_grid(P, 8), TS_T, 0, c->st>>>(c->h.bytes, off, P, (unsigned long long *)pslot, (uint32_t *)pcnt, S - 1, ctl);
+        HIPCHK(hipGetLastError());
+        if ((r = ts_read_ctl(c, ctl, hc))) return r;
+        if (!hc[TSC_FULL]) break;
+        if (S >= smax) return fail(BPE_GPU_EINTERNAL, "train_split: the piece table is full at its largest size");
+        S *= 4;
+    }
+    *slots = S;
+    *nlong = hc[TSC_LONG];
+    const uint64_t ne = (uint64_t)hc[TSC_LONG] + hc[TSC_CLAIMED];
+    if (ne == 0 || ne > P) return fail(BPE_GPU_EINTERNAL, "train_split: entry count out of range");
+    void *k0, *v0, *k1, *v1, *est, *elen, *eoff, *tmp;
+    if ((r = dscratch(c, 19, ne * 4, &k0)) || (r = dscratch(c, 20, ne * 4, &v0)) || (r = dscratch(c, 21, ne * 4, &k1)) ||
+        (r = dscratch(c, 22, ne * 4, &v1)) || (r = dscratch(c, 23, ne * 8, &est)) || (r = dscratch(c, 24, (ne + 1) * 4, &elen)) ||
+        (r = dscratch(c, 25, (ne + 1) * 4, &eoff)))
+        return r;
+    k_ts_collect_slots<<<ts_grid(S), TS_T, 0, c->st>>>((const unsigned long long *)pslot, (const uint32_t *)pcnt, S, ctl,
+                                                      (uint32_t *)k0, (uint32_t *)v0, ne);
+    HIPCHK(hipGetLastError());
+    if (hc[TSC_LONG]) {
+        k_ts_collect_long<<<ts_grid(P), TS_T, 0, c->st>>>(off, P, ctl, (uint32_t *)k0, (uint32_t *)v0, ne);
+        HIPCHK(hipGetLastError());
+    }
+    size_t tb = 0, tb2 = 0;
+    HIPCHK(rocprim::radix_sort_pairs(nullptr, tb, (uint32_t *)k0, (uint32_t *)k1, (uint32_t *)v0, (uint32_t *)v1, ne, 0, 32, c->st));
+    HIPCHK(rocprim::exclusive_scan(nullptr, tb2, (uint32_t *)elen, (uint32_t *)eoff, 0u, ne + 1, rocprim::plus<uint32_t>(), c->st));
+    tb = std::max(tb, tb2);
+    if ((r = dscratch(c, 26, tb, &tmp))) return r;
+    HIPCHK(rocprim::radix_sort_pairs(tmp, tb, (uint32_t *)k0, (uint32_t *)k1, (uint32_t *)v0, (uint32_t *)v1, ne, 0, 32, c->st));
+    k_ts_entries<<<(uint32_t)((ne + TS_T) / TS_T), TS_T, 0, c->st>>>(off, (const uint32_t *)k1, ne, (uint64_t *)est, (uint32_t *)elen);
+    HIPCHK(hipGetLastError());
+    HIPCHK(rocprim::exclusive_scan(tmp, tb, (uint32_t *)elen, (uint32_t *)eoff, 0u, ne + 1, rocprim::plus<uint32_t>(), c->st));
+    uint32_t total = 0;
+    HIPCHK(hipMemcpyAsync(&total, (uint32_t *)eoff + ne, 4, hipMemcpyDeviceToHost, c->st));
+    if ((r = ts_read_ctl(c, ctl, hc))) return r;
+    if (hc[TSC_APPEND] != ne) return fail(BPE_GPU_EINTERNAL, "train_split: entry records do not match their count");
+    if (total < ne || total > c->n0) return fail(BPE_GPU_EINTERNAL, "train_split: entry bytes out of range");
+    *E = ne;
+    *T = total;
+    return 0;
+}
+
+int bpe_gpu_train_split(bpe_gpu_ctx *c, long max_merges, size_t *n_merges) {
+    if (!c || !n_merges) return BPE_GPU_EINVAL;
+    if (!c->loaded) return fail(BPE_GPU_ESTATE, "train_split before load");
+    if (!c->split_ready) return fail(BPE_GPU_ESTATE, "train_split: no split of the loaded bytes");
+    HIPCHK(hipSetDevice(c->dev));
+    c->ts_ready = false;
+    c->ts_merges.clear();
+    uint64_t cap = engine_merge_cap();
+    bool own_cap = true;
+    if (max_merges >= 0 && (uint64_t)max_merges <= cap) {
+        cap = (uint64_t)max_merges;
+        own_cap = false;
+    }
+    int r;
+    void *p;
+    if ((r = dscratch(c, 18, 16 * 4, &p))) return r;
+    uint32_t *ctl = (uint32_t *)p;
+    uint32_t hc[16];
+    uint64_t E = 0, T = 0, nlong = 0, slots = 0;
+    if (c->split_n && (r = ts_piece_table(c, ctl, &E, &T, &nlong, &slots))) return r;
+    const uint64_t T0 = T;
+    uint64_t stop = 0;
+    // Stage B: tok / ent ping-pong (27-30), keep and its scan (31, 32), run heads and their scan (33, 34)
+    uint32_t *tok[2] = {}, *ent[2] = {}, *keep = nullptr, *pos = nullptr, *hv = nullptr, *rs = nullptr;
+    void *tmp = nullptr;
+    size_t tb = 0;
+    if (T) {
+        void *q[8];
+        for (int k = 0; k < 8; k++)
+            if ((r = dscratch(c, 27 + k, (T + 1) * 4, &q[k]))) return r;
+        tok[0] = (uint32_t *)q[0], tok[1] = (uint32_t *)q[1], ent[0] = (uint32_t *)q[2], ent[1] = (uint32_t *)q[3];
+        keep = (uint32_t *)q[4], pos = (uint32_t *)q[5], hv = (uint32_t *)q[6], rs = (uint32_t *)q[7];
+        size_t t1 = 0, t2 = 0;
+        HIPCHK(rocprim::exclusive_scan(nullptr, t1, keep, pos, 0u, T + 1, rocprim::plus<uint32_t>(), c->st));
+        HIPCHK(rocprim::inclusive_scan(nullptr, t2, hv, rs, T, rocprim::maximum<uint32_t>(), c->st));
+        tb = std::max(t1, t2);
+        if ((r = dscratch(c, 26, tb, &tmp))) return r;
+        k_ts_gather<<<ts_grid(T), TS_T, 0, c->st>>>(c->h.bytes, (const uint64_t *)c->dscr[23], (const uint32_t *)c->dscr[25],
+                                                   (uint32_t)E, (uint32_t)T, tok[0], ent[0]);
+        HIPCHK(hipGetLastError());
+    }
+    const uint32_t *ecnt = (const uint32_t *)c->dscr[22];
+    // the pair table starts at 2 T slots or 2^20 and grows like the piece table
+    const uint64_t pmax = std::max<uint64_t>(pow2_at_least(2 * T), 1024) * 16;
+    uint64_t Sp = std::min<uint64_t>(std::max<uint64_t>(pow2_at_least(2 * T), 1024), 1u << 20);
+    void *part;
+    if ((r = dscratch(c, 37, (size_t)TS_GRID * 16, &part))) return r;
+    int cur = 0;
+    for (uint64_t m = 0;; m++) {
+        uint32_t best = 0, a = 0, b = 0;
+        if (T >= 2) {
+            for (;;) {
+                void *pk, *pc;
+                if ((r = dscratch(c, 35, Sp * 8, &pk)) || (r = dscratch(c, 36, Sp * 4, &pc))) return r;
+                HIPCHK(hipMemsetAsync(pk, 0xFF, Sp * 8, c->st));
+                HIPCHK(hipMemsetAsync(pc, 0, Sp * 4, c->st));
+                HIPCHK(hipMemsetAsync(ctl, 0, 16 * 4, c->st));
+                k_tb_count<<<ts_grid(T, 16), TB_CT, 0, c->st>>>(tok[cur], ent[cur], ecnt, (uint32_t)T, (unsigned long long *)pk,
+                                                              (uint32_t *)pc, Sp - 1, ctl);
+                HIPCHK(hipGetLastError());
+                const uint32_t nb = ts_grid(Sp, 4);
+                k_tb_argmax<<<nb, TS_T, 0, c->st>>>((const unsigned long long *)pk, (const uint32_t *)pc, Sp, (unsigned long long *)part);
+                HIPCHK(hipGetLastError());
+                k_tb_argmax2<<<1, TS_T, 0, c->st>>>((const unsigned long long *)part, nb, ctl);
+                HIPCHK(hipGetLastError());
+                if ((r = ts_read_ctl(c, ctl, hc))) return r;
+                if (!hc[TSC_PFULL]) break;
+                if (Sp >= pmax) return fail(BPE_GPU_EINTERNAL, "train_split: the pair table is full at its largest size");
+                Sp *= 4;
+            }
+            best = hc[TSC_CNT], a = hc[TSC_A], b = hc[TSC_B];
+        }
+        if (best <= 1) {  // the reference's rule first: no pair left, or none seen twice
+            stop = 1;
+            break;
+        }
+        if (m == cap) {
+            stop = own_cap ? 3 : 2;
+            break;
+        }
+        const uint32_t z = 256u + (uint32_t)m, g = ts_grid(T, 4);
+        const uint32_t *runs = nullptr;
+        if (a == b) {
+            k_tb_heads<<<g, TS_T, 0, c->st>>>(tok[cur], ent[cur], (uint32_t)T, a, hv);
+            HIPCHK(hipGetLastError());
+            HIPCHK(rocprim::inclusive_scan(tmp, tb, hv, rs, T, rocprim::maximum<uint32_t>(), c->st));
+            runs = rs;
+        }
+        k_tb_flag<<<g, TS_T, 0, c->st>>>(tok[cur], ent[cur], runs, (uint32_t)T, a, b, keep);
+        HIPCHK(hipGetLastError());
+        HIPCHK(rocprim::exclusive_scan(tmp, tb, keep, pos, 0u, T + 1, rocprim::plus<uint32_t>(), c->st));
+        k_tb_scatter<<<g, TS_T, 0, c->st>>>(tok[cur], ent[cur], keep, pos, (uint32_t)T, z, tok[cur ^ 1], ent[cur ^ 1]);
+        HIPCHK(hipGetLastError());
+        uint32_t newT = 0;
+        HIPCHK(hipMemcpyAsync(&newT, pos + T, 4, hipMemcpyDeviceToHost, c->st));
+        HIPCHK(hipStreamSynchronize(c->st));
+        if (newT >= T || newT < E) return fail(BPE_GPU_EINTERNAL, "train_split: a merge removed no token or too many");
+        T = newT;
+        cur ^= 1;
+        c->ts_merges.push_back(a);
+        c->ts_merges.push_back(b);
+    }
+    if (stop == 3)
+        fprintf(stderr,
+                "bpe: training stopped at the engine's merge cap (%llu merges) before the reference's stop rule "
+                "(max count <= 1); pass a merge cap to choose the length\n",
+                (unsigned long long)cap);
+    const uint64_t info[8] = {c->split_n, E, T0, nlong, c->ts_merges.size() / 2, stop, TS_DEDUP_MAX, slots};
+    memcpy(c->ts_info, info, sizeof info);
+    c->ts_ready = true;
+    *n_merges = c->ts_merges.size() / 2;
+    return 0;
+}
+
+int bpe_gpu_fetch_split_merges(bpe_gpu_ctx *c, uint32_t *out, size_t cap, size_t *count) {
+    if (!c || !count) return BPE_GPU_EINVAL;
+    if (!c->loaded || !c->split_ready || !c->ts_ready) return fail(BPE_GPU_ESTATE, "no split merges: train_split first");
+    const size_t k = c->ts_merges.size() / 2;
+    *count = k;
+    if (out) memcpy(out, c->ts_merges.data(), std::min(cap, k) * 8);
+    return 0;
+}
+
+int bpe_gpu_train_split_info(bpe_gpu_ctx *c, uint64_t *out8) {
+    if (!c || !out8) return BPE_GPU_EINVAL;
+    if (!c->loaded || !c->split_ready || !c->ts_ready) return fail(BPE_GPU_ESTATE, "no split training: train_split first");
+    memcpy(out8, c->ts_info, sizeof c->ts_info);
+    return 0;
+}
+
+int bpe_gpu_fetch_piece_table(bpe_gpu_ctx *c, uint64_t *start, uint32_t *len, uint32_t *count, size_t cap, size_t *entries) {
+    if (!c || !entries) return BPE_GPU_EINVAL;
+    if (!c->loaded || !c->split_ready || !c->ts_ready) return fail(BPE_GPU_ESTATE, "no piece table: train_split first");
+    HIPCHK(hipSetDevice(c->dev));
+    *entries = (size_t)c->ts_info[1];
+    const size_t k = std::min<size_t>(cap, *entries);
+    int r;
+    if (k && start && (r = d2h_staged(c, start, c->dscr[23], k * 8))) return r;
+    if (k && len && (r = d2h_staged(c, len, c->dscr[24], k * 4))) return r;
+    if (k && count && (r = d2h_staged(c, count, c->dscr[22], k * 4))) return r;
+    return 0;
 }
 
 int bpe_gpu_fetch_doc_offsets(bpe_gpu_ctx *c, uint64_t *out, size_t cap, size_t *count) {

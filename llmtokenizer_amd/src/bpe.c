@@ -258,7 +258,7 @@ void bpe_release_engines(void)
 }
 
 /* merges (pairs) -> a reference-shaped merge list */
-static dyn_arr_t *pairs_to_arr(const uint32_t *pairs, size_t k)
+dyn_arr_t *pairs_to_arr(const uint32_t *pairs, size_t k)
 {
     dyn_arr_t *arr = new_pair_arr();
     for (size_t r = 0; arr && r < k; r++) {
