@@ -20,6 +20,10 @@ COBJ_GPU := $(patsubst $(PKG)/src/%.c,$(BUILD)/%.o,$(CSRC_GPU))
 # a list of its own (tests/asan_train_split has the model for it)
 CSRC_TS := $(PKG)/src/bpe_train_split.c
 COBJ_TS := $(patsubst $(PKG)/src/%.c,$(BUILD)/%.o,$(CSRC_TS))
+# host code over bpe_gpu_split_preset, which none of those models has: a list of its own again
+# (tests/asan_split_preset has the model for it)
+CSRC_SP := $(PKG)/src/bpe_split_preset.c
+COBJ_SP := $(patsubst $(PKG)/src/%.c,$(BUILD)/%.o,$(CSRC_SP))
 HIPDEPS := $(wildcard $(PKG)/csrc/*.hip $(PKG)/csrc/*.h) include/bpe_gpu.h
 
 all: $(PKG)/libbpe_amd.so tools/bpe_main oracle
@@ -33,7 +37,7 @@ $(BUILD)/engine.o: $(HIPDEPS) | $(BUILD)
 $(BUILD)/%.o: $(PKG)/src/%.c $(wildcard include/*.h $(PKG)/src/*.h) | $(BUILD)
 	$(CC) $(CFLAGS) -c $< -o $@
 
-$(PKG)/libbpe_amd.so: $(BUILD)/engine.o $(COBJ) $(COBJ_GPU) $(COBJ_TS)
+$(PKG)/libbpe_amd.so: $(BUILD)/engine.o $(COBJ) $(COBJ_GPU) $(COBJ_TS) $(COBJ_SP)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -lm -ldl -lpthread
 
 tools/bpe_main: tools/bpe_main.c $(PKG)/libbpe_amd.so
@@ -76,3 +80,15 @@ tests/asan_train_split/asan_train_split: tests/asan_train_split/asan_train_split
 
 asan-train-split: tests/asan_train_split/asan_train_split
 .PHONY: asan-train-split
+
+# the preset rules' host code (src/bpe_split_preset.c: the rules in plain C and the two _preset entry
+# points, which run the bodies in src/bpe_docs.c and src/bpe_train_split.c) the same way, against a host
+# model of the engine calls they make (tests/asan_split_preset/asan_split_preset.c); run by
+# tests/test_asan_split_preset.py
+SP_SRCS := $(CSRC) $(CSRC_GPU) $(CSRC_TS) $(CSRC_SP)
+tests/asan_split_preset/asan_split_preset: tests/asan_split_preset/asan_split_preset.c $(SP_SRCS) $(wildcard include/*.h $(PKG)/src/*.h)
+	$(CC) -O1 -g -std=c11 -D_GNU_SOURCE -fno-omit-frame-pointer -fsanitize=address,undefined \
+	    -fno-sanitize-recover=undefined -Iinclude -o $@ tests/asan_split_preset/asan_split_preset.c $(SP_SRCS) -lm -lpthread
+
+asan-split-preset: tests/asan_split_preset/asan_split_preset
+.PHONY: asan-split-preset

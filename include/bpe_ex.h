@@ -74,7 +74,21 @@ uint32_t *bpe_encode_split(const uint8_t *bytes, size_t n, const uint8_t *cls, c
 dyn_arr_t *bpe_train_split(const uint8_t *bytes, size_t n, const uint8_t *cls, const uint16_t *brk, long max_merges,
                            int device);
 
-/* statistics of the last compress/compress_ex/bpe_train_bytes/bpe_encode_bytes/bpe_encode_docs/bpe_encode_split */
+/* The preset split rules (bpe_gpu.h: BPE_SPLIT_LINES, BPE_SPLIT_WORDS, BPE_SPLIT_GPT2) in plain C, on
+ * the host and without a GPU: the written definition bpe_gpu_split_preset is held to, and the
+ * yardstick for inputs too large for a regular-expression engine.  Two-phase like the fetch calls:
+ * out may be NULL, *count = pieces + 1 (the piece starts followed by n; n == 0: the single offset 0),
+ * and at most cap entries are written.  BPE_GPU_EINVAL for another preset or a bad argument. */
+int bpe_split_offsets_host(int preset, const uint8_t *bytes, size_t n, uint64_t *out, size_t cap, size_t *count);
+
+/* bpe_encode_split with a preset in place of the tables (bpe_gpu_split_preset): the way to
+ * BPE_SPLIT_GPT2, which no two tables express.  Results and ownership as bpe_encode_split. */
+uint32_t *bpe_encode_split_preset(const uint8_t *bytes, size_t n, int preset, dyn_arr_t *pair_arr, int device,
+                                  size_t *len, uint64_t **id_off, uint64_t **byte_off, size_t *ndocs);
+/* bpe_train_split with a preset in place of the tables */
+dyn_arr_t *bpe_train_split_preset(const uint8_t *bytes, size_t n, int preset, long max_merges, int device);
+
+/* statistics of the last compress/compress_ex/bpe_train_bytes/bpe_encode_bytes/bpe_encode_docs/bpe_encode_split(_preset) */
 int bpe_last_stats(bpe_gpu_stats *out);
 
 /* compress / compress_ex / bpe_train_bytes / bpe_encode_bytes / decompress keep

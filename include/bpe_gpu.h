@@ -251,8 +251,8 @@ int bpe_gpu_docs_window(const uint64_t *doc_off, size_t ndocs, uint64_t n,
  * the single offset 0).  They stay in HBM and are bpe_gpu_encode_docs' doc_off
  * for bpe_gpu_encode_split: no host copy of them is made on the way.
  *
- * The presets are this project's own rules, NOT GPT-2's regular expression:
- * no contractions, no look-ahead, no Unicode classes.
+ * The two table presets are this project's own rules, NOT GPT-2's regular
+ * expression: no contractions, no look-ahead, no Unicode classes.
  *   BPE_SPLIT_LINES  class 1 is '\n', the rest 0; brk[1] = 0x3: a piece ends
  *                    after each newline and keeps it.
  *   BPE_SPLIT_WORDS  class 1 letters A-Z a-z and every byte >= 0x80 (a UTF-8
@@ -263,6 +263,32 @@ int bpe_gpu_docs_window(const uint64_t *doc_off, size_t ndocs, uint64_t n,
  *                    attach to what follows them): brk[p] = 0x1F & ~(1 << p)
  *                    for p in 0, 1, 2, 4 and brk[3] = 1 << 4.
  *
+ * BPE_SPLIT_GPT2 is no table rule (bpe_gpu_split_rule returns BPE_GPU_EINVAL
+ * for it; bpe_gpu_split_preset runs it).  Its pieces are the successive matches
+ * of the bytes pattern
+ *   's|'t|'re|'ve|'m|'ll|'d| ?[A-Za-z\x80-\xff]+| ?[0-9]+| ?[^\sA-Za-z0-9\x80-\xff]+|\s+(?!\S)|\s+
+ * which is GPT-2's alternation with \p{L}, \p{N} and \s replaced by the byte
+ * classes of BPE_SPLIT_WORDS (L letters and bytes >= 0x80, N digits, S the
+ * space, W \t \n \v \f \r, P the rest, NUL and the apostrophe included; "ws" is
+ * S or W).  On printable ASCII text with \t \n \v \f \r that is GPT-2's
+ * alternation by construction; on any other input it is this project's
+ * byte-level reading of the pattern (every byte >= 0x80 a letter, no Unicode
+ * classes), and nothing more is claimed.  The contractions are lower case only.
+ * As a function of the bytes around i (0 < i < n; c, p the classes of b[i],
+ * b[i - 1]), with clen(j) = the length of a contraction at j: 0 unless b[j] is
+ * the apostrophe, j == 0 or the class of b[j - 1] is L, N or W, and the bytes
+ * after j inside the text begin with s, t, re, ve, m, ll or d; then 2 or 3:
+ *   c ws:               a start if p is not ws, or if i + 1 < n and b[i + 1] is
+ *                       not ws (the last white-space byte before text splits
+ *                       off; a run that reaches the end stays whole);
+ *   c not ws, p is S:   no start (the space belongs to what follows it);
+ *   c not ws, p is W:   a start;
+ *   neither is ws:      no start if clen(i - 1) >= 2 or clen(i - 2) == 3 (inside
+ *                       a contraction); else a start if clen(i - 2) == 2 or
+ *                       clen(i - 3) == 3 (one ended at i - 1); else c != p.
+ * So a start depends on b[i - 4 .. i + 1] and on n alone.  bpe_ex.h's
+ * bpe_split_offsets_host is this rule in plain C.
+ *
  * The offsets belong to the loaded bytes.  bpe_gpu_load / _load_fd / _synth /
  * _trim, bpe_gpu_train / _train_ex and a sharded group's load, synth and train
  * on the context drop them; bpe_gpu_encode, _encode_docs, _encode_split and
@@ -270,17 +296,21 @@ int bpe_gpu_docs_window(const uint64_t *doc_off, size_t ndocs, uint64_t n,
  * bpe_gpu_split replaces them.  A call that needs them and finds none returns
  * BPE_GPU_ESTATE.
  * ---------------------------------------------------------------------- */
-enum { BPE_SPLIT_LINES = 0, BPE_SPLIT_WORDS = 1 };
+enum { BPE_SPLIT_LINES = 0, BPE_SPLIT_WORDS = 1, BPE_SPLIT_GPT2 = 2 };
 /* bytes one workgroup of the split kernels handles per step, and the largest grid
    (a corpus of more than TILE * GRID bytes is walked in grid strides) */
 #define BPE_GPU_SPLIT_TILE 4096
 #define BPE_GPU_SPLIT_GRID 2048
-/* fill cls[256] / brk[16] with a preset (pure function, no GPU) */
+/* fill cls[256] / brk[16] with a table preset (pure function, no GPU); BPE_SPLIT_GPT2 has no tables: BPE_GPU_EINVAL */
 int bpe_gpu_split_rule(int preset, uint8_t *cls, uint16_t *brk);
 /* out4 = {BPE_GPU_SPLIT_TILE, BPE_GPU_SPLIT_TILE * BPE_GPU_SPLIT_GRID, 0, 0} (pure function, no GPU) */
 int bpe_gpu_split_info(uint64_t *out4);
 /* split the loaded bytes; *ndocs = pieces.  A cls entry above 15 is BPE_GPU_EINVAL. */
 int bpe_gpu_split(bpe_gpu_ctx *ctx, const uint8_t *cls, const uint16_t *brk, size_t *ndocs);
+/* the same by a preset: BPE_SPLIT_LINES / BPE_SPLIT_WORDS are bpe_gpu_split with their tables, BPE_SPLIT_GPT2
+   marks the starts with a kernel of its own; the offsets and all that is said of them above are the same.
+   BPE_GPU_EINVAL for another preset, BPE_GPU_ESTATE before a load. */
+int bpe_gpu_split_preset(bpe_gpu_ctx *ctx, int preset, size_t *ndocs);
 /* the last split's offsets; out may be NULL, *count = ndocs + 1 */
 int bpe_gpu_fetch_split_offsets(bpe_gpu_ctx *ctx, uint64_t *out, size_t cap, size_t *count);
 /* bpe_gpu_encode_docs over the last split's offsets (resident: neither checked nor uploaded);

@@ -22,7 +22,7 @@ EXPORTS = [
     # bpe_ex.h
     "compress_ex", "bpe_train_bytes", "bpe_encode_bytes", "bpe_last_stats",
     "bpe_train_bytes_devices", "compress_multi", "bpe_release_engines", "bpe_encode_docs", "bpe_decode_docs",
-    "bpe_encode_split", "bpe_train_split",
+    "bpe_encode_split", "bpe_train_split", "bpe_split_offsets_host", "bpe_encode_split_preset", "bpe_train_split_preset",
     # bpe_gpu.h
     "bpe_gpu_device_count", "bpe_gpu_create", "bpe_gpu_destroy", "bpe_gpu_load", "bpe_gpu_synth",
     "bpe_gpu_train", "bpe_gpu_fetch_merges", "bpe_gpu_fetch_ids", "bpe_gpu_encode", "bpe_gpu_decode",
@@ -42,6 +42,7 @@ EXPORTS = [
     "bpe_gpu_docs_window",
     # bpe_gpu.h: splitting the resident bytes
     "bpe_gpu_split_rule", "bpe_gpu_split_info", "bpe_gpu_split", "bpe_gpu_fetch_split_offsets", "bpe_gpu_encode_split",
+    "bpe_gpu_split_preset",
     # bpe_gpu.h: training on the pieces
     "bpe_gpu_train_split", "bpe_gpu_fetch_split_merges", "bpe_gpu_train_split_info", "bpe_gpu_fetch_piece_table",
 ]
@@ -205,6 +206,13 @@ def load():
     L.bpe_gpu_fetch_piece_table.argtypes = [vp, vp, vp, vp, sz, ctypes.POINTER(sz)]
     L.bpe_train_split.argtypes = [vp, sz, vp, vp, ctypes.c_long, ctypes.c_int]
     L.bpe_train_split.restype = ctypes.POINTER(DynArr)
+    L.bpe_gpu_split_preset.argtypes = [vp, ctypes.c_int, ctypes.POINTER(sz)]
+    L.bpe_split_offsets_host.argtypes = [ctypes.c_int, vp, sz, vp, sz, ctypes.POINTER(sz)]
+    L.bpe_encode_split_preset.argtypes = [vp, sz, ctypes.c_int, ctypes.POINTER(DynArr), ctypes.c_int, ctypes.POINTER(sz),
+                                          ctypes.POINTER(u64p), ctypes.POINTER(u64p), ctypes.POINTER(sz)]
+    L.bpe_encode_split_preset.restype = u32p
+    L.bpe_train_split_preset.argtypes = [vp, sz, ctypes.c_int, ctypes.c_long, ctypes.c_int]
+    L.bpe_train_split_preset.restype = ctypes.POINTER(DynArr)
     L.bpe_release_engines.argtypes = []
     L.bpe_release_engines.restype = None
     _LIB = L

@@ -172,15 +172,20 @@ def encode_batch(docs, merges, device=0):
     return _take_ids(p, n.value), offsets
 
 
-SPLIT_PRESETS = {"lines": 0, "words": 1}  # bpe_gpu.h BPE_SPLIT_LINES / BPE_SPLIT_WORDS
+SPLIT_PRESETS = {"lines": 0, "words": 1, "gpt2": 2}  # bpe_gpu.h BPE_SPLIT_LINES / BPE_SPLIT_WORDS / BPE_SPLIT_GPT2
+TABLE_PRESETS = ("lines", "words")  # the presets two tables express
 
 
 def split_rule(preset):
     """The tables (cls uint8[256], brk uint16[16]) of a preset split rule, "lines"
     or "words" (bpe_gpu.h bpe_gpu_split_rule; this project's rules, not GPT-2's
     regular expression): a piece starts at byte i when bit cls[b[i]] of
-    brk[cls[b[i - 1]]] is set, and at byte 0."""
-    if preset not in SPLIT_PRESETS:
+    brk[cls[b[i - 1]]] is set, and at byte 0.  "gpt2" has no tables (a start
+    there depends on six bytes): pass the name to split / encode_split /
+    train_split / split_host."""
+    if preset == "gpt2":
+        raise BpeError('split_rule: the rule "gpt2" has no tables: pass its name as the rule')
+    if preset not in TABLE_PRESETS:
         raise BpeError(f"split_rule: no preset {preset!r} (have {sorted(SPLIT_PRESETS)})")
     L = _lib.load()
     cls = np.zeros(256, dtype=np.uint8)
@@ -188,6 +193,25 @@ def split_rule(preset):
     _lib.check(L.bpe_gpu_split_rule(SPLIT_PRESETS[preset], cls.ctypes.data_as(ctypes.c_void_p),
                                     brk.ctypes.data_as(ctypes.c_void_p)), "split_rule")
     return cls, brk
+
+
+def split_host(data: bytes, rule):
+    """The offsets (uint64: the piece starts followed by len(data)) of a preset
+    rule, "lines", "words" or "gpt2", computed on the host in plain C
+    (bpe_ex.h bpe_split_offsets_host): the definition Engine.split(rule) is held
+    to.  No GPU."""
+    if not isinstance(rule, str) or rule not in SPLIT_PRESETS:
+        raise BpeError(f"split_host: no preset {rule!r} (have {sorted(SPLIT_PRESETS)})")
+    L = _lib.load()
+    buf = np.frombuffer(data, dtype=np.uint8)
+    vp = ctypes.c_void_p
+    cnt = ctypes.c_size_t(0)
+    _lib.check(L.bpe_split_offsets_host(SPLIT_PRESETS[rule], buf.ctypes.data_as(vp), buf.size, None, 0,
+                                        ctypes.byref(cnt)), "split_host")
+    out = np.zeros(cnt.value, dtype=np.uint64)
+    _lib.check(L.bpe_split_offsets_host(SPLIT_PRESETS[rule], buf.ctypes.data_as(vp), buf.size, out.ctypes.data_as(vp),
+                                        out.size, ctypes.byref(cnt)), "split_host")
+    return out
 
 
 def split_info():
@@ -208,21 +232,27 @@ def _rule_tables(rule):
 
 
 def encode_split(data: bytes, merges, rule="words", device=0):
-    """Split data into pieces on the GPU (rule: a preset name or a (cls, brk)
-    pair, see split_rule) and encode the pieces as documents.  Returns (ids,
+    """Split data into pieces on the GPU (rule: a preset name, "lines", "words" or
+    "gpt2", or a (cls, brk) pair, see split_rule) and encode the pieces as documents.  Returns (ids,
     id_offsets, byte_offsets), both offsets uint64 of length pieces + 1: piece d
     is data[byte_offsets[d]:byte_offsets[d + 1]] and its ids are
     ids[id_offsets[d]:id_offsets[d + 1]] == encode(piece d, merges)."""
     L = _lib.load()
-    cls, brk = _rule_tables(rule)
+    gpt2 = isinstance(rule, str) and rule == "gpt2"
+    cls, brk = (None, None) if gpt2 else _rule_tables(rule)
     buf = np.frombuffer(data, dtype=np.uint8)
     arr = _merges_to_arr(merges)
     n, nd = ctypes.c_size_t(0), ctypes.c_size_t(0)
     ido, bo = ctypes.POINTER(ctypes.c_uint64)(), ctypes.POINTER(ctypes.c_uint64)()
     vp = ctypes.c_void_p
     try:
-        p = L.bpe_encode_split(buf.ctypes.data_as(vp), buf.size, cls.ctypes.data_as(vp), brk.ctypes.data_as(vp), arr,
-                               int(device), ctypes.byref(n), ctypes.byref(ido), ctypes.byref(bo), ctypes.byref(nd))
+        if gpt2:
+            p = L.bpe_encode_split_preset(buf.ctypes.data_as(vp), buf.size, SPLIT_PRESETS[rule], arr, int(device),
+                                          ctypes.byref(n), ctypes.byref(ido), ctypes.byref(bo), ctypes.byref(nd))
+        else:
+            p = L.bpe_encode_split(buf.ctypes.data_as(vp), buf.size, cls.ctypes.data_as(vp), brk.ctypes.data_as(vp),
+                                   arr, int(device), ctypes.byref(n), ctypes.byref(ido), ctypes.byref(bo),
+                                   ctypes.byref(nd))
     finally:
         L.dyn_arr_free(arr)
     if not p:
@@ -240,11 +270,15 @@ def train_split(data: bytes, rule="words", max_merges=-1, device=0):
     rule can apply every one of them (bpe_ex.h bpe_train_split).  Returns the
     merges, (k, 2) uint32 for ids 256..255+k."""
     L = _lib.load()
-    cls, brk = _rule_tables(rule)
     buf = np.frombuffer(data, dtype=np.uint8)
     vp = ctypes.c_void_p
-    arr = L.bpe_train_split(buf.ctypes.data_as(vp), buf.size, cls.ctypes.data_as(vp), brk.ctypes.data_as(vp),
-                            int(max_merges), int(device))
+    if isinstance(rule, str) and rule == "gpt2":
+        arr = L.bpe_train_split_preset(buf.ctypes.data_as(vp), buf.size, SPLIT_PRESETS[rule], int(max_merges),
+                                       int(device))
+    else:
+        cls, brk = _rule_tables(rule)
+        arr = L.bpe_train_split(buf.ctypes.data_as(vp), buf.size, cls.ctypes.data_as(vp), brk.ctypes.data_as(vp),
+                                int(max_merges), int(device))
     if not arr:
         raise BpeError("bpe_train_split failed")
     try:
@@ -375,10 +409,13 @@ class Engine:
 
     def split(self, rule="words"):
         """split the resident bytes into pieces on the device (rule: a preset
-        name or a (cls, brk) pair, see split_rule); the offsets stay in HBM for
+        name, "lines", "words" or "gpt2", or a (cls, brk) pair, see split_rule); the offsets stay in HBM for
         encode_split().  Returns the number of pieces."""
-        cls, brk = _rule_tables(rule)
         nd = ctypes.c_size_t(0)
+        if isinstance(rule, str) and rule == "gpt2":  # no tables: the preset call (bpe_gpu_split_preset)
+            _lib.check(self.L.bpe_gpu_split_preset(self.ctx, SPLIT_PRESETS[rule], ctypes.byref(nd)), "split")
+            return nd.value
+        cls, brk = _rule_tables(rule)
         _lib.check(self.L.bpe_gpu_split(self.ctx, cls.ctypes.data_as(ctypes.c_void_p),
                                         brk.ctypes.data_as(ctypes.c_void_p), ctypes.byref(nd)), "split")
         return nd.value

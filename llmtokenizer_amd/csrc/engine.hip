@@ -3400,6 +3400,7 @@ int bpe_gpu_split_rule(int preset, uint8_t *cls, uint16_t *brk) {
         brk[1] = 0x3;
         return 0;
     }
+    if (preset == BPE_SPLIT_GPT2) return fail(BPE_GPU_EINVAL, "split_rule: BPE_SPLIT_GPT2 has no tables (bpe_gpu_split_preset)");
     if (preset != BPE_SPLIT_WORDS) return fail(BPE_GPU_EINVAL, "split_rule: no such preset");
     for (int b = 0; b < 256; b++)
         cls[b] = (b >= 'A' && b <= 'Z') || (b >= 'a' && b <= 'z') || b >= 0x80 ? 1
@@ -3420,13 +3421,9 @@ int bpe_gpu_split_info(uint64_t *out4) {
     return 0;
 }
 
-int bpe_gpu_split(bpe_gpu_ctx *c, const uint8_t *cls, const uint16_t *brk, size_t *ndocs) {
-    if (!c || !cls || !brk || !ndocs) return BPE_GPU_EINVAL;
-    if (!c->loaded) return fail(BPE_GPU_ESTATE, "split before load");
-    SplitRule R;
-    for (int b = 0; b < 256; b++)
-        if ((R.cls[b] = cls[b]) > 15) return fail(BPE_GPU_EINVAL, "split: a class above 15");
-    memcpy(R.brk, brk, sizeof R.brk);
+// the body of bpe_gpu_split (R: the tables) and of bpe_gpu_split_preset's BPE_SPLIT_GPT2 (R == nullptr): all but
+// the marking launch is one code, so the offsets and their lifetime are the same whichever kernel marked the starts
+static int split_run(bpe_gpu_ctx *c, const SplitRule *R, size_t *ndocs) {
     HIPCHK(hipSetDevice(c->dev));
     c->split_ready = false;
     c->ts_ready = false;  // bpe_gpu_train_split's results describe the offsets replaced here
@@ -3436,9 +3433,9 @@ int bpe_gpu_split(bpe_gpu_ctx *c, const uint8_t *cls, const uint16_t *brk, size_
     unsigned long long *woff = nullptr;
     int r;
     if (n) {
-        void *tbl, *pm, *pc, *tmp;
+        void *tbl = nullptr, *pm, *pc, *tmp;
         // counts [nwt + 1] (the last one 0) and their scan [nwt + 1] in one slot
-        if ((r = dscratch(c, 12, SP_TBL * 4, &tbl)) || (r = dscratch(c, 13, ntiles * SP_T * 2, &pm)) ||
+        if ((R && (r = dscratch(c, 12, SP_TBL * 4, &tbl))) || (r = dscratch(c, 13, ntiles * SP_T * 2, &pm)) ||
             (r = dscratch(c, 14, (nwt + 1) * 8 + ((nwt + 1) * 4 + 7) / 8 * 8, &pc)))
             return r;
         mask = (uint16_t *)pm;
@@ -3446,9 +3443,13 @@ int bpe_gpu_split(bpe_gpu_ctx *c, const uint8_t *cls, const uint16_t *brk, size_
         uint32_t *wcnt = (uint32_t *)(woff + nwt + 1);
         const uint32_t grid = (uint32_t)std::min<uint64_t>(ntiles, SP_GRID);
         HIPCHK(hipMemsetAsync(wcnt + nwt, 0, 4, c->st));
-        k_split_table<<<SP_TBL / SP_T, SP_T, 0, c->st>>>(R, (uint32_t *)tbl);
-        HIPCHK(hipGetLastError());
-        k_split_mark<<<grid, SP_T, 0, c->st>>>(c->h.bytes, n, (const uint32_t *)tbl, ntiles, mask, wcnt);
+        if (R) {
+            k_split_table<<<SP_TBL / SP_T, SP_T, 0, c->st>>>(*R, (uint32_t *)tbl);
+            HIPCHK(hipGetLastError());
+            k_split_mark<<<grid, SP_T, 0, c->st>>>(c->h.bytes, n, (const uint32_t *)tbl, ntiles, mask, wcnt);
+        } else {
+            k_split_mark_gpt2<<<grid, SP_T, 0, c->st>>>(c->h.bytes, n, ntiles, mask, wcnt);
+        }
         HIPCHK(hipGetLastError());
         size_t tb = 0;
         HIPCHK(rocprim::exclusive_scan(nullptr, tb, wcnt, woff, 0ull, nwt + 1, rocprim::plus<unsigned long long>(), c->st));
@@ -3483,6 +3484,30 @@ int bpe_gpu_split(bpe_gpu_ctx *c, const uint8_t *cls, const uint16_t *brk, size_
     c->split_ready = true;
     *ndocs = (size_t)total;
     return 0;
+}
+
+int bpe_gpu_split(bpe_gpu_ctx *c, const uint8_t *cls, const uint16_t *brk, size_t *ndocs) {
+    if (!c || !cls || !brk || !ndocs) return BPE_GPU_EINVAL;
+    if (!c->loaded) return fail(BPE_GPU_ESTATE, "split before load");
+    SplitRule R;
+    for (int b = 0; b < 256; b++)
+        if ((R.cls[b] = cls[b]) > 15) return fail(BPE_GPU_EINVAL, "split: a class above 15");
+    memcpy(R.brk, brk, sizeof R.brk);
+    return split_run(c, &R, ndocs);
+}
+
+int bpe_gpu_split_preset(bpe_gpu_ctx *c, int preset, size_t *ndocs) {
+    if (!c || !ndocs) return BPE_GPU_EINVAL;
+    if (preset != BPE_SPLIT_LINES && preset != BPE_SPLIT_WORDS && preset != BPE_SPLIT_GPT2)
+        return fail(BPE_GPU_EINVAL, "split_preset: no such preset");
+    if (preset == BPE_SPLIT_GPT2) {
+        if (!c->loaded) return fail(BPE_GPU_ESTATE, "split before load");
+        return split_run(c, nullptr, ndocs);
+    }
+    uint8_t cls[256];
+    uint16_t brk[16];
+    const int r = bpe_gpu_split_rule(preset, cls, brk);
+    return r ? r : bpe_gpu_split(c, cls, brk, ndocs);
 }
 
 int bpe_gpu_fetch_split_offsets(bpe_gpu_ctx *c, uint64_t *out, size_t cap, size_t *count) {

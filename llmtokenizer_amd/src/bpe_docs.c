@@ -2,7 +2,8 @@
  * bpe_docs.c -- document batches of bpe_ex.h: bpe_encode_docs / bpe_decode_docs
  * over the engine's bpe_gpu_encode_docs / bpe_gpu_decode_docs, and
  * bpe_encode_split over bpe_gpu_split / bpe_gpu_encode_split, on the cached
- * engine contexts of bpe.c.
+ * engine contexts of bpe.c.  encode_split_with is its body with the split step
+ * passed in: bpe_split_preset.c runs it over bpe_gpu_split_preset.
  */
 #include "bpe_internal.h"
 
@@ -45,7 +46,15 @@ done:
 uint32_t *bpe_encode_split(const uint8_t *bytes, size_t n, const uint8_t *cls, const uint16_t *brk, dyn_arr_t *pair_arr,
                            int device, size_t *len, uint64_t **id_off, uint64_t **byte_off, size_t *ndocs)
 {
-    if ((!bytes && n) || !cls || !brk || !pair_arr || !len || !id_off || !ndocs) return NULL;
+    if (!cls || !brk) return NULL;
+    const struct split_tables t = {cls, brk};
+    return encode_split_with(bytes, n, split_tables, &t, pair_arr, device, len, id_off, byte_off, ndocs);
+}
+
+uint32_t *encode_split_with(const uint8_t *bytes, size_t n, bpe_split_fn split, const void *rule, dyn_arr_t *pair_arr,
+                            int device, size_t *len, uint64_t **id_off, uint64_t **byte_off, size_t *ndocs)
+{
+    if ((!bytes && n) || !pair_arr || !len || !id_off || !ndocs) return NULL;
     bpe_gpu_ctx *ctx = NULL;
     size_t k = 0, n_ids = 0, n_off = 0, pieces = 0;
     uint32_t *pairs = arr_to_pairs(pair_arr, &k), *ids = NULL;
@@ -54,7 +63,7 @@ uint32_t *bpe_encode_split(const uint8_t *bytes, size_t n, const uint8_t *cls, c
     if (!pairs) return NULL;
     if ((rc = open_engine(device, &ctx))) goto done;
     if ((rc = bpe_gpu_load(ctx, bytes, n))) { report("load", rc); goto done; }
-    if ((rc = bpe_gpu_split(ctx, cls, brk, &pieces))) { report("split", rc); goto done; }
+    if ((rc = split(ctx, rule, &pieces))) { report("split", rc); goto done; }
     if ((rc = bpe_gpu_encode_split(ctx, pairs, k))) { report("encode split", rc); goto done; }
     if ((rc = bpe_gpu_fetch_ids(ctx, NULL, 0, &n_ids))) { report("fetch ids", rc); goto done; }
     ids = alloc_ids(n_ids);

@@ -1,0 +1,91 @@
+/*
+ * bpe_split_preset.c -- the preset split rules of bpe_ex.h: the rules in plain C
+ * (bpe_split_offsets_host: the written definition the device kernels are held
+ * to, no GPU), and bpe_encode_split_preset / bpe_train_split_preset over
+ * bpe_gpu_split_preset, on the bodies bpe_encode_split and bpe_train_split run.
+ */
+#include "bpe_internal.h"
+
+enum { C_P = 0, C_L = 1, C_N = 2, C_S = 3, C_W = 4 }; /* the classes of BPE_SPLIT_WORDS and BPE_SPLIT_GPT2 */
+
+static int class_of(uint8_t b)
+{
+    return (b >= 'A' && b <= 'Z') || (b >= 'a' && b <= 'z') || b >= 0x80 ? C_L
+           : b >= '0' && b <= '9'                                        ? C_N
+           : b == ' '                                                    ? C_S
+           : b >= '\t' && b <= '\r'                                      ? C_W
+                                                                         : C_P;
+}
+
+/* BPE_SPLIT_GPT2: the length (2 or 3) of a contraction piece that starts at byte j < n, or 0 */
+static int clen(const uint8_t *b, size_t n, size_t j)
+{
+    if (b[j] != '\'' || j + 1 >= n) return 0;
+    if (j) {
+        const int p = class_of(b[j - 1]);
+        if (p != C_L && p != C_N && p != C_W) return 0; /* a space or punctuation takes the apostrophe along */
+    }
+    const uint8_t x = b[j + 1];
+    if (x == 's' || x == 't' || x == 'm' || x == 'd') return 2;
+    if (j + 2 >= n) return 0;
+    const uint8_t y = b[j + 2];
+    return ((x == 'r' || x == 'v') && y == 'e') || (x == 'l' && y == 'l') ? 3 : 0;
+}
+
+/* does a piece start at byte i, 0 < i < n? */
+static int starts_gpt2(const uint8_t *b, size_t n, size_t i)
+{
+    const int c = class_of(b[i]), p = class_of(b[i - 1]);
+    const int cw = c == C_S || c == C_W, pw = p == C_S || p == C_W;
+    if (cw) {
+        if (!pw) return 1;
+        if (i + 1 >= n) return 0; /* a run that reaches the end of the text stays whole */
+        const int x = class_of(b[i + 1]);
+        return x != C_S && x != C_W; /* the last white-space byte before text splits off */
+    }
+    if (pw) return p == C_W; /* a space belongs to what follows it */
+    if (clen(b, n, i - 1) >= 2 || (i >= 2 && clen(b, n, i - 2) == 3)) return 0;
+    if ((i >= 2 && clen(b, n, i - 2) == 2) || (i >= 3 && clen(b, n, i - 3) == 3)) return 1;
+    return c != p;
+}
+
+static int starts_words(const uint8_t *b, size_t i)
+{
+    const int c = class_of(b[i]), p = class_of(b[i - 1]);
+    return p == C_S ? c == C_W : c != p;
+}
+
+int bpe_split_offsets_host(int preset, const uint8_t *bytes, size_t n, uint64_t *out, size_t cap, size_t *count)
+{
+    if ((!bytes && n) || !count) return BPE_GPU_EINVAL;
+    if (preset != BPE_SPLIT_LINES && preset != BPE_SPLIT_WORDS && preset != BPE_SPLIT_GPT2) return BPE_GPU_EINVAL;
+    size_t k = 0;
+    for (size_t i = 0; i < n; i++) {
+        const int s = i == 0                     ? 1
+                      : preset == BPE_SPLIT_GPT2 ? starts_gpt2(bytes, n, i)
+                      : preset == BPE_SPLIT_WORDS ? starts_words(bytes, i)
+                                                  : bytes[i - 1] == '\n';
+        if (!s) continue;
+        if (out && k < cap) out[k] = i;
+        k++;
+    }
+    if (out && k < cap) out[k] = n;
+    *count = k + 1;
+    return 0;
+}
+
+static int split_preset(bpe_gpu_ctx *ctx, const void *rule, size_t *pieces)
+{
+    return bpe_gpu_split_preset(ctx, *(const int *)rule, pieces);
+}
+
+uint32_t *bpe_encode_split_preset(const uint8_t *bytes, size_t n, int preset, dyn_arr_t *pair_arr, int device,
+                                  size_t *len, uint64_t **id_off, uint64_t **byte_off, size_t *ndocs)
+{
+    return encode_split_with(bytes, n, split_preset, &preset, pair_arr, device, len, id_off, byte_off, ndocs);
+}
+
+dyn_arr_t *bpe_train_split_preset(const uint8_t *bytes, size_t n, int preset, long max_merges, int device)
+{
+    return train_split_with(bytes, n, split_preset, &preset, max_merges, device);
+}

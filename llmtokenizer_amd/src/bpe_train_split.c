@@ -1,7 +1,9 @@
 /*
  * bpe_train_split.c -- bpe_train_split of bpe_ex.h: load, bpe_gpu_split and
  * bpe_gpu_train_split on the cached engine contexts of bpe.c, the merges
- * returned in the shape compress() returns them.
+ * returned in the shape compress() returns them.  train_split_with is its body
+ * with the split step passed in: bpe_split_preset.c runs it over
+ * bpe_gpu_split_preset.
  */
 #include "bpe_internal.h"
 
@@ -10,7 +12,15 @@
 dyn_arr_t *bpe_train_split(const uint8_t *bytes, size_t n, const uint8_t *cls, const uint16_t *brk, long max_merges,
                            int device)
 {
-    if ((!bytes && n) || !cls || !brk) return NULL;
+    if (!cls || !brk) return NULL;
+    const struct split_tables t = {cls, brk};
+    return train_split_with(bytes, n, split_tables, &t, max_merges, device);
+}
+
+dyn_arr_t *train_split_with(const uint8_t *bytes, size_t n, bpe_split_fn split, const void *rule, long max_merges,
+                            int device)
+{
+    if (!bytes && n) return NULL;
     bpe_gpu_ctx *ctx = NULL;
     size_t k = 0, got = 0, pieces = 0;
     uint32_t *pairs = NULL;
@@ -18,7 +28,7 @@ dyn_arr_t *bpe_train_split(const uint8_t *bytes, size_t n, const uint8_t *cls, c
     int rc;
     if ((rc = open_engine(device, &ctx))) goto done;
     if ((rc = bpe_gpu_load(ctx, bytes, n))) { report("load", rc); goto done; }
-    if ((rc = bpe_gpu_split(ctx, cls, brk, &pieces))) { report("split", rc); goto done; }
+    if ((rc = split(ctx, rule, &pieces))) { report("split", rc); goto done; }
     if ((rc = bpe_gpu_train_split(ctx, max_merges, &k))) { report("train split", rc); goto done; }
     pairs = malloc((k ? k : 1) * 2 * sizeof(uint32_t));
     if (!pairs) goto done;

@@ -4,7 +4,8 @@ encode_split against the host-offset path it replaces.
 
 Two 1 GiB corpora resident in HBM: the seed-3 synthetic corpus (Engine.synth;
 printable bytes, no newline) and english_like (a 32 MiB sample generated on the
-host and repeated to the size).  Two rules, "lines" and "words".
+host and repeated to the size).  Three rules: the table rules "lines" and
+"words", and "gpt2" (bpe_gpu_split_preset; its own marking kernel).
 
   split    Engine.split(rule) alone, alternated with a device-to-device
            hipMemcpyAsync of the same number of bytes timed the same way (host
@@ -13,12 +14,17 @@ host and repeated to the size).  Two rules, "lines" and "words".
            (n read, n / 8 of start masks written and read again, 8 B per offset
            written, 12 B per 1,024 bytes of counts and their scan) per second,
            and that rate over the copy's (2 n bytes per copy).
+  split_ab per corpus, Engine.split("words") and Engine.split("gpt2") alternated in
+           one loop: the two marking kernels side by side (their emit passes
+           differ by the piece counts only).
   e2e      per corpus and rule, alternated in one process:
              resident  Engine.split + Engine.encode_split
              host      Engine.encode_docs(offsets, merges) with the same offsets
                        from host memory (what the library offered before), and
-                       the time numpy takes to make them (the rule's
-                       restatement, in 32 MiB chunks), reported apart
+                       the time the host takes to make them (numpy's
+                       restatement of the tables in 32 MiB chunks; for
+                       "gpt2" api.split_host, the rule in plain C),
+                       reported apart
              single    Engine.encode(merges), the single-stream ceiling
            with the merge list of tools/docs_bench.py (the first --merges
            merges the trainer learns on the 1 GiB seed-2 corpus).
@@ -115,7 +121,7 @@ def main():
         sys.exit("split_bench: no GPU")
     reps = max(5, args.repeats)
     n = args.size
-    out = {"tool": "split_bench", "bytes": n, "split": {}, "e2e": {}}
+    out = {"tool": "split_bench", "bytes": n, "split": {}, "split_ab": {}, "e2e": {}}
     merges = None
     if not args.no_e2e:
         tr = api.Engine(args.device)
@@ -134,7 +140,7 @@ def main():
         else:
             host = np.tile(sample, (n + sample.size - 1) // sample.size)[:n]
             e.load(host.tobytes())
-        for rule in ("lines", "words"):
+        for rule in ("lines", "words", "gpt2"):
             key = f"{corpus}/{rule}"
             nd = e.split(rule)  # warm
             cp.run()
@@ -157,9 +163,8 @@ def main():
                 continue
             if host is None:  # the parent path's user holds the text on the host
                 host = np.frombuffer(synth_bytes(3, n), np.uint8)
-            cls, brk = api.split_rule(rule)
             t0 = time.perf_counter()
-            off = restate(host, cls, brk)
+            off = api.split_host(host, rule) if rule == "gpt2" else restate(host, *api.split_rule(rule))
             t_numpy = time.perf_counter() - t0
             if off.size - 1 != nd or not (e.split_offsets() == off).all():
                 sys.exit(f"split_bench: {key}: the device's offsets differ from the restatement")
@@ -189,7 +194,8 @@ def main():
             out["e2e"][key] = {
                 "pieces": int(nd), "resident": r, "resident_split_part": med(t_res_split),
                 "resident_encode_part": med([a - b for a, b in zip(t_res, t_res_split)]), "host_offsets": h,
-                "numpy_offsets_ms": round(t_numpy * 1e3, 1), "single": s, "docs_info": info,
+                "numpy_offsets_ms": round(t_numpy * 1e3, 1), "offsets_made_by": "split_host" if rule == "gpt2" else "numpy",
+                "single": s, "docs_info": info,
                 "resident_gbps": round(n / r["ms_median"] / 1e6, 2), "host_gbps": round(n / h["ms_median"] / 1e6, 2),
                 "host_with_numpy_gbps": round(n / (h["ms_median"] + t_numpy * 1e3) / 1e6, 3),
                 "single_gbps": round(n / s["ms_median"] / 1e6, 2),
@@ -198,6 +204,13 @@ def main():
                 "single_spread": round((s["ms_max"] - s["ms_min"]) / s["ms_median"], 4)}
             del off
             print(json.dumps({"progress": key, **out["e2e"][key]}), file=sys.stderr, flush=True)
+        ab = {"words": [], "gpt2": []}
+        for _ in range(reps):
+            for rule, ts in ab.items():
+                t0 = time.perf_counter()
+                e.split(rule)
+                ts.append(time.perf_counter() - t0)
+        out["split_ab"][corpus] = {rule: med(ts) for rule, ts in ab.items()}
     e.close()
     cp.close()
     print(json.dumps(out))
