@@ -24,6 +24,12 @@ COBJ_TS := $(patsubst $(PKG)/src/%.c,$(BUILD)/%.o,$(CSRC_TS))
 # (tests/asan_split_preset has the model for it)
 CSRC_SP := $(PKG)/src/bpe_split_preset.c
 COBJ_SP := $(patsubst $(PKG)/src/%.c,$(BUILD)/%.o,$(CSRC_SP))
+# the special tokens: src/bpe_special.c is host code alone (the set's check and the split's definition; no
+# engine call, so tests/asan_special needs no model), src/bpe_special_gpu.c the entry points over
+# bpe_gpu_split_special & co., which none of the models above has
+CSRC_SPECIAL := $(PKG)/src/bpe_special.c
+CSRC_SPECIAL_GPU := $(PKG)/src/bpe_special_gpu.c
+COBJ_SPECIAL := $(patsubst $(PKG)/src/%.c,$(BUILD)/%.o,$(CSRC_SPECIAL) $(CSRC_SPECIAL_GPU))
 HIPDEPS := $(wildcard $(PKG)/csrc/*.hip $(PKG)/csrc/*.h) include/bpe_gpu.h
 
 all: $(PKG)/libbpe_amd.so tools/bpe_main oracle
@@ -37,7 +43,7 @@ $(BUILD)/engine.o: $(HIPDEPS) | $(BUILD)
 $(BUILD)/%.o: $(PKG)/src/%.c $(wildcard include/*.h $(PKG)/src/*.h) | $(BUILD)
 	$(CC) $(CFLAGS) -c $< -o $@
 
-$(PKG)/libbpe_amd.so: $(BUILD)/engine.o $(COBJ) $(COBJ_GPU) $(COBJ_TS) $(COBJ_SP)
+$(PKG)/libbpe_amd.so: $(BUILD)/engine.o $(COBJ) $(COBJ_GPU) $(COBJ_TS) $(COBJ_SP) $(COBJ_SPECIAL)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -lm -ldl -lpthread
 
 tools/bpe_main: tools/bpe_main.c $(PKG)/libbpe_amd.so
@@ -92,3 +98,13 @@ tests/asan_split_preset/asan_split_preset: tests/asan_split_preset/asan_split_pr
 
 asan-split-preset: tests/asan_split_preset/asan_split_preset
 .PHONY: asan-split-preset
+
+# the special tokens' host definition (src/bpe_special.c, over bpe_split_offsets_host of src/bpe_split_preset.c)
+# the same way, in a stand-alone program that calls no engine function (tests/asan_special/asan_special.c and
+# its stubs for what bpe_split_preset.c's entry points reference); run by tests/test_asan_special.py
+tests/asan_special/asan_special: tests/asan_special/asan_special.c $(CSRC_SPECIAL) $(CSRC_SP) $(wildcard include/*.h $(PKG)/src/*.h)
+	$(CC) -O1 -g -std=c11 -D_GNU_SOURCE -fno-omit-frame-pointer -fsanitize=address,undefined \
+	    -fno-sanitize-recover=undefined -Iinclude -o $@ tests/asan_special/asan_special.c $(CSRC_SPECIAL) $(CSRC_SP) -lm
+
+asan-special: tests/asan_special/asan_special
+.PHONY: asan-special

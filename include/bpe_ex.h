@@ -88,6 +88,33 @@ uint32_t *bpe_encode_split_preset(const uint8_t *bytes, size_t n, int preset, dy
 /* bpe_train_split with a preset in place of the tables */
 dyn_arr_t *bpe_train_split_preset(const uint8_t *bytes, size_t n, int preset, long max_merges, int device);
 
+/* Special tokens (bpe_gpu.h, "Special tokens": the set, the overlap-free condition, the split, the ids).
+ * bpe_specials_check: 0 when `specials` (NULL or count 0: the empty set) keeps the limits and the
+ * overlap-free condition; else BPE_GPU_EINVAL and, unless msg is NULL, a message in msg[0 .. msg_cap)
+ * that names the special or the pair at fault by index and text.  No GPU. */
+int bpe_specials_check(const bpe_gpu_specials *specials, char *msg, size_t msg_cap);
+/* bpe_split_offsets_host with specials, for a preset or, with preset < 0, for the tables cls[256] / brk[16]:
+ * the matches found byte by byte, every segment between them split as a text of its own.  This is the
+ * written definition bpe_gpu_split_special is held to.  out / cap / count as bpe_split_offsets_host;
+ * sp_piece / sp_index (either may be NULL) receive at most sp_cap special pieces in order, the piece's
+ * index among the offsets and the special's index in the caller's list, *sp_count (may be NULL) their
+ * number.  BPE_GPU_EINVAL for a set bpe_specials_check refuses, a class above 15 or a bad argument. */
+int bpe_split_offsets_host_special(int preset, const uint8_t *cls, const uint16_t *brk, const uint8_t *bytes, size_t n,
+                                   const bpe_gpu_specials *specials, uint64_t *out, size_t cap, size_t *count,
+                                   uint64_t *sp_piece, uint32_t *sp_index, size_t sp_cap, size_t *sp_count);
+/* bpe_encode_split / bpe_encode_split_preset with specials (preset < 0: the tables): every occurrence of
+ * special j is one piece with the one id 256 + merges + j.  Results and ownership as bpe_encode_split. */
+uint32_t *bpe_encode_split_special(const uint8_t *bytes, size_t n, int preset, const uint8_t *cls, const uint16_t *brk,
+                                   const bpe_gpu_specials *specials, dyn_arr_t *pair_arr, int device, size_t *len,
+                                   uint64_t **id_off, uint64_t **byte_off, size_t *ndocs);
+/* bpe_train_split / bpe_train_split_preset with specials: the special pieces are no part of the corpus */
+dyn_arr_t *bpe_train_split_special(const uint8_t *bytes, size_t n, int preset, const uint8_t *cls, const uint16_t *brk,
+                                   const bpe_gpu_specials *specials, long max_merges, int device);
+/* bpe_decode_docs with specials: id 256 + merges + j expands to special j's bytes.  id_off may be NULL
+ * with ndocs == 0: the ids are one flat sequence and *byte_off is not written. */
+char *bpe_decode_docs_special(const uint32_t *ids, size_t len, const uint64_t *id_off, size_t ndocs, dyn_arr_t *pair_arr,
+                              const bpe_gpu_specials *specials, int device, size_t *out_len, uint64_t **byte_off);
+
 /* statistics of the last compress/compress_ex/bpe_train_bytes/bpe_encode_bytes/bpe_encode_docs/bpe_encode_split(_preset) */
 int bpe_last_stats(bpe_gpu_stats *out);
 

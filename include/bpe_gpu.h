@@ -351,6 +351,79 @@ int bpe_gpu_train_split_info(bpe_gpu_ctx *ctx, uint64_t *out8);
 int bpe_gpu_fetch_piece_table(bpe_gpu_ctx *ctx, uint64_t *start, uint32_t *len, uint32_t *count, size_t cap,
                               size_t *entries);
 
+/* ------------------------------------------------------------------------
+ * Special tokens: literals such as <|endoftext|> that are found in the raw
+ * bytes before the rule runs, become exactly one reserved id each, never merge
+ * with their neighbours and take no part in training.  This project's
+ * definition:
+ *
+ * The set.  S byte strings, 0 <= S <= 256, each 1..64 bytes long (64 is the
+ * longest piece bpe_gpu_train_split deduplicates, so a special is always one
+ * entry of the piece table) and without a NUL byte (the loaders end the text at
+ * the first NUL and the decoders drop NULs).
+ *
+ * The overlap-free condition.  No special is a substring of another (which
+ * makes them distinct), and no non-empty proper suffix of a special is a prefix
+ * of a special, the same one included ("aa" is refused).  Two occurrences of
+ * specials in a text then never overlap and never start at the same byte, so
+ * "all occurrences" is a pure function of at most 64 bytes from each position
+ * and equals the successive matches of the alternation of the specials in any
+ * list order.  <|endoftext|>, the ChatML markers and <|reserved_special_token_N|>
+ * satisfy it.  Any other set is BPE_GPU_EINVAL, the message naming the pair
+ * (bpe_ex.h bpe_specials_check); leftmost / list-order matching of overlapping
+ * sets is not offered.
+ *
+ * The split.  Every occurrence [s, e) of a special in the loaded bytes is one
+ * piece.  Each maximal stretch between two matches (and from byte 0 to the first,
+ * from the last to n) is a segment, split by the rule as a text of its own with
+ * its offsets shifted by its start.  For a table rule a piece therefore starts
+ * at every s and every e < n, none inside a match, and every other byte is
+ * decided as without specials.  For BPE_SPLIT_GPT2 the bytes near a match read
+ * differently: looking back from byte i, everything at or before the nearest
+ * match byte reads as a newline; looking ahead, a match byte reads as a space, as
+ * the bytes at and past n do.  Only positions s - 1 and e .. e + 3 can differ
+ * from the marks without specials.  With S == 0 the offsets are those of
+ * bpe_gpu_split / bpe_gpu_split_preset.
+ *
+ * Ids.  Special j (the caller's list order) has the id 256 + n_merges + j for
+ * the merge list of the call at hand.  bpe_gpu_encode_split after such a split
+ * leaves exactly that one id for a special piece, counted by the id offsets;
+ * every other piece encodes as without specials.  bpe_gpu_train_split leaves
+ * the special pieces out of the corpus: they add no pair and the piece table
+ * does not list them; out8[0] stays the split's piece count.
+ * bpe_gpu_decode_docs_special expands an id in [256 + n_merges, 256 + n_merges +
+ * S) to its special's bytes; larger ids remain unknown.
+ *
+ * The specials and the list of special pieces belong to the split's offsets:
+ * what drops those drops these, and a bpe_gpu_split or bpe_gpu_split_preset
+ * afterwards is a split without specials.
+ * ---------------------------------------------------------------------- */
+#define BPE_GPU_SPECIAL_MAX_COUNT 256
+#define BPE_GPU_SPECIAL_MAX_LEN 64
+/* special j is bytes[len[0] + .. + len[j - 1] ..] of len[j] bytes */
+typedef struct {
+    const uint8_t *bytes;
+    const uint32_t *len;
+    size_t count;
+} bpe_gpu_specials;
+/* split the loaded bytes by a preset, or with preset < 0 by the tables cls / brk (ignored otherwise), around
+   the specials (NULL or count 0: exactly bpe_gpu_split / bpe_gpu_split_preset).  BPE_GPU_EINVAL, before any
+   launch, for a set that breaks the limits or the overlap-free condition. */
+int bpe_gpu_split_special(bpe_gpu_ctx *ctx, int preset, const uint8_t *cls, const uint16_t *brk,
+                          const bpe_gpu_specials *specials, size_t *ndocs);
+/* out4 = {S, matches, passes of the find kernel (2 when the match list had to grow), entries the match list
+   holds} of the last split (zeros after one without specials) */
+int bpe_gpu_split_special_info(bpe_gpu_ctx *ctx, uint64_t *out4);
+/* the special pieces of the last split in order: the piece's index among the offsets and the special's index;
+   either array may be NULL, *count = matches */
+int bpe_gpu_fetch_special_pieces(bpe_gpu_ctx *ctx, uint64_t *piece, uint32_t *index, size_t cap, size_t *count);
+/* bpe_gpu_decode_docs with specials.  id_off may be NULL with ndocs == 0: the ids are one flat sequence
+   (bpe_gpu_decode) and byte_off is not written. */
+int bpe_gpu_decode_docs_special(bpe_gpu_ctx *ctx, const uint32_t *ids, size_t len, const uint64_t *id_off,
+                                size_t ndocs, const uint32_t *pairs, size_t n_merges,
+                                const bpe_gpu_specials *specials, uint8_t *out, size_t cap, size_t *out_len,
+                                uint64_t *byte_off);
+
 int bpe_gpu_get_stats(bpe_gpu_ctx *ctx, bpe_gpu_stats *st);
 
 /* Position-keyed checksum of the ids of the last train / encode, computed in

@@ -45,7 +45,16 @@ EXPORTS = [
     "bpe_gpu_split_preset",
     # bpe_gpu.h: training on the pieces
     "bpe_gpu_train_split", "bpe_gpu_fetch_split_merges", "bpe_gpu_train_split_info", "bpe_gpu_fetch_piece_table",
+    # bpe_gpu.h / bpe_ex.h: special tokens
+    "bpe_gpu_split_special", "bpe_gpu_split_special_info", "bpe_gpu_fetch_special_pieces", "bpe_gpu_decode_docs_special",
+    "bpe_specials_check", "bpe_split_offsets_host_special", "bpe_encode_split_special", "bpe_train_split_special",
+    "bpe_decode_docs_special",
 ]
+
+
+class Specials(ctypes.Structure):
+    """bpe_gpu.h bpe_gpu_specials"""
+    _fields_ = [("bytes", ctypes.c_void_p), ("len", ctypes.c_void_p), ("count", ctypes.c_size_t)]
 
 
 class GpuStats(ctypes.Structure):
@@ -213,6 +222,23 @@ def load():
     L.bpe_encode_split_preset.restype = u32p
     L.bpe_train_split_preset.argtypes = [vp, sz, ctypes.c_int, ctypes.c_long, ctypes.c_int]
     L.bpe_train_split_preset.restype = ctypes.POINTER(DynArr)
+    spp = ctypes.POINTER(Specials)
+    L.bpe_gpu_split_special.argtypes = [vp, ctypes.c_int, vp, vp, spp, ctypes.POINTER(sz)]
+    L.bpe_gpu_split_special_info.argtypes = [vp, vp]
+    L.bpe_gpu_fetch_special_pieces.argtypes = [vp, vp, vp, sz, ctypes.POINTER(sz)]
+    L.bpe_gpu_decode_docs_special.argtypes = [vp, vp, sz, vp, sz, vp, sz, spp, vp, sz, ctypes.POINTER(sz), vp]
+    L.bpe_specials_check.argtypes = [spp, ctypes.c_char_p, sz]
+    L.bpe_split_offsets_host_special.argtypes = [ctypes.c_int, vp, vp, vp, sz, spp, vp, sz, ctypes.POINTER(sz), vp, vp, sz,
+                                                 ctypes.POINTER(sz)]
+    L.bpe_encode_split_special.argtypes = [vp, sz, ctypes.c_int, vp, vp, spp, ctypes.POINTER(DynArr), ctypes.c_int,
+                                           ctypes.POINTER(sz), ctypes.POINTER(u64p), ctypes.POINTER(u64p),
+                                           ctypes.POINTER(sz)]
+    L.bpe_encode_split_special.restype = u32p
+    L.bpe_train_split_special.argtypes = [vp, sz, ctypes.c_int, vp, vp, spp, ctypes.c_long, ctypes.c_int]
+    L.bpe_train_split_special.restype = ctypes.POINTER(DynArr)
+    L.bpe_decode_docs_special.argtypes = [vp, sz, vp, sz, ctypes.POINTER(DynArr), spp, ctypes.c_int, ctypes.POINTER(sz),
+                                          ctypes.POINTER(u64p)]
+    L.bpe_decode_docs_special.restype = ctypes.c_void_p
     L.bpe_release_engines.argtypes = []
     L.bpe_release_engines.restype = None
     _LIB = L

@@ -195,11 +195,69 @@ def split_rule(preset):
     return cls, brk
 
 
-def split_host(data: bytes, rule):
+class _Specials:
+    """bpe_gpu.h bpe_gpu_specials over a list of bytes-like specials (keeps the buffers it points to)"""
+
+    def __init__(self, specials):
+        items = [bytes(s) for s in specials]
+        self.blob = np.frombuffer(b"".join(items) + b"\0", dtype=np.uint8)  # (+ a byte: never an empty buffer)
+        self.len = np.array([len(s) for s in items] + [0], dtype=np.uint32)
+        self.c = _lib.Specials(self.blob.ctypes.data, self.len.ctypes.data, len(items))
+        self.ref = ctypes.byref(self.c)
+
+
+def check_specials(specials):
+    """Raise BpeError unless `specials` (a list of bytes-like objects) is a set the split accepts: at most 256
+    of 1..64 bytes each, no NUL byte, none a substring of another, no proper suffix of one a prefix of one
+    (bpe_gpu.h, "Special tokens"; bpe_ex.h bpe_specials_check).  The message names the pair.  Returns the set as the C calls take it.  No GPU."""
+    sp = specials if isinstance(specials, _Specials) else _Specials(specials)
+    msg = ctypes.create_string_buffer(400)
+    if _lib.load().bpe_specials_check(sp.ref, msg, len(msg)):
+        raise BpeError(msg.value.decode(errors="replace"))
+    return sp
+
+
+def _rule_args(rule):
+    """(preset or -1, cls pointer, brk pointer, the arrays to keep) of a rule for the *_special calls"""
+    if isinstance(rule, str):
+        if rule not in SPLIT_PRESETS:
+            raise BpeError(f"no preset {rule!r} (have {sorted(SPLIT_PRESETS)})")
+        return SPLIT_PRESETS[rule], None, None, None
+    cls, brk = _rule_tables(rule)
+    return -1, cls.ctypes.data_as(ctypes.c_void_p), brk.ctypes.data_as(ctypes.c_void_p), (cls, brk)
+
+
+def split_host_special(data: bytes, rule, specials):
+    """(offsets, special piece indices, their specials' indices) of the split with specials computed on the
+    host in plain C (bpe_ex.h bpe_split_offsets_host_special): the definition Engine.split(rule, specials) is
+    held to.  rule: a preset name or a (cls, brk) pair.  No GPU."""
+    sp = check_specials(specials)
+    L = _lib.load()
+    preset, pc, pb, keep = _rule_args(rule)
+    buf = np.frombuffer(data, dtype=np.uint8)
+    vp = ctypes.c_void_p
+    cnt, m = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    _lib.check(L.bpe_split_offsets_host_special(preset, pc, pb, buf.ctypes.data_as(vp), buf.size, sp.ref, None, 0,
+                                                ctypes.byref(cnt), None, None, 0, ctypes.byref(m)), "split_host")
+    out = np.zeros(cnt.value, dtype=np.uint64)
+    piece = np.zeros(max(m.value, 1), dtype=np.uint64)
+    index = np.zeros(max(m.value, 1), dtype=np.uint32)
+    _lib.check(L.bpe_split_offsets_host_special(preset, pc, pb, buf.ctypes.data_as(vp), buf.size, sp.ref,
+                                                out.ctypes.data_as(vp), out.size, ctypes.byref(cnt),
+                                                piece.ctypes.data_as(vp), index.ctypes.data_as(vp), m.value,
+                                                ctypes.byref(m)), "split_host")
+    return out, piece[: m.value], index[: m.value]
+
+
+def split_host(data: bytes, rule, specials=None):
     """The offsets (uint64: the piece starts followed by len(data)) of a preset
     rule, "lines", "words" or "gpt2", computed on the host in plain C
     (bpe_ex.h bpe_split_offsets_host): the definition Engine.split(rule) is held
-    to.  No GPU."""
+    to.  With specials (a list of bytes-like objects, see check_specials) the
+    definition of Engine.split(rule, specials), for a preset or a (cls, brk)
+    pair (split_host_special also returns which pieces are specials).  No GPU."""
+    if specials is not None:
+        return split_host_special(data, rule, specials)[0]
     if not isinstance(rule, str) or rule not in SPLIT_PRESETS:
         raise BpeError(f"split_host: no preset {rule!r} (have {sorted(SPLIT_PRESETS)})")
     L = _lib.load()
@@ -231,22 +289,31 @@ def _rule_tables(rule):
     return cls, brk
 
 
-def encode_split(data: bytes, merges, rule="words", device=0):
+def encode_split(data: bytes, merges, rule="words", device=0, specials=None):
     """Split data into pieces on the GPU (rule: a preset name, "lines", "words" or
     "gpt2", or a (cls, brk) pair, see split_rule) and encode the pieces as documents.  Returns (ids,
     id_offsets, byte_offsets), both offsets uint64 of length pieces + 1: piece d
     is data[byte_offsets[d]:byte_offsets[d + 1]] and its ids are
-    ids[id_offsets[d]:id_offsets[d + 1]] == encode(piece d, merges)."""
+    ids[id_offsets[d]:id_offsets[d + 1]] == encode(piece d, merges).  With specials (a list of
+    bytes-like objects, see check_specials) every occurrence of specials[j] is a piece of its own
+    with the one id 256 + len(merges) + j."""
     L = _lib.load()
+    if specials is not None:
+        check_specials(specials)
     gpt2 = isinstance(rule, str) and rule == "gpt2"
-    cls, brk = (None, None) if gpt2 else _rule_tables(rule)
+    cls, brk = (None, None) if gpt2 or specials is not None else _rule_tables(rule)
     buf = np.frombuffer(data, dtype=np.uint8)
     arr = _merges_to_arr(merges)
     n, nd = ctypes.c_size_t(0), ctypes.c_size_t(0)
     ido, bo = ctypes.POINTER(ctypes.c_uint64)(), ctypes.POINTER(ctypes.c_uint64)()
     vp = ctypes.c_void_p
     try:
-        if gpt2:
+        if specials is not None:
+            sp = _Specials(specials)
+            preset, pc, pb, keep = _rule_args(rule)
+            p = L.bpe_encode_split_special(buf.ctypes.data_as(vp), buf.size, preset, pc, pb, sp.ref, arr, int(device),
+                                           ctypes.byref(n), ctypes.byref(ido), ctypes.byref(bo), ctypes.byref(nd))
+        elif gpt2:
             p = L.bpe_encode_split_preset(buf.ctypes.data_as(vp), buf.size, SPLIT_PRESETS[rule], arr, int(device),
                                           ctypes.byref(n), ctypes.byref(ido), ctypes.byref(bo), ctypes.byref(nd))
         else:
@@ -264,15 +331,22 @@ def encode_split(data: bytes, merges, rule="words", device=0):
     return _take_ids(p, n.value), id_off, byte_off
 
 
-def train_split(data: bytes, rule="words", max_merges=-1, device=0):
+def train_split(data: bytes, rule="words", max_merges=-1, device=0, specials=None):
     """Split data into pieces on the GPU (rule as in encode_split) and train on the
     pieces: merges that never cross a piece boundary, so encode_split with the same
     rule can apply every one of them (bpe_ex.h bpe_train_split).  Returns the
-    merges, (k, 2) uint32 for ids 256..255+k."""
+    merges, (k, 2) uint32 for ids 256..255+k.  With specials (see encode_split) their
+    occurrences are pieces that take no part in the training."""
     L = _lib.load()
     buf = np.frombuffer(data, dtype=np.uint8)
     vp = ctypes.c_void_p
-    if isinstance(rule, str) and rule == "gpt2":
+    if specials is not None:
+        check_specials(specials)
+        sp = _Specials(specials)
+        preset, pc, pb, keep = _rule_args(rule)
+        arr = L.bpe_train_split_special(buf.ctypes.data_as(vp), buf.size, preset, pc, pb, sp.ref, int(max_merges),
+                                        int(device))
+    elif isinstance(rule, str) and rule == "gpt2":
         arr = L.bpe_train_split_preset(buf.ctypes.data_as(vp), buf.size, SPLIT_PRESETS[rule], int(max_merges),
                                        int(device))
     else:
@@ -287,19 +361,28 @@ def train_split(data: bytes, rule="words", max_merges=-1, device=0):
         L.dyn_arr_free(arr)
 
 
-def decode_batch(ids, offsets, merges, device=0):
-    """Inverse of encode_batch: the list of the documents' bytes (NUL bytes dropped, as decompress does)."""
+def decode_batch(ids, offsets, merges, device=0, specials=None):
+    """Inverse of encode_batch: the list of the documents' bytes (NUL bytes dropped, as decompress does).
+    With specials (see encode_split) the id 256 + len(merges) + j is specials[j]."""
     L = _lib.load()
     ids = np.ascontiguousarray(ids, dtype=np.uint32)
     off = _doc_offsets(offsets)
     if off.size < 1:
         raise BpeError("decode_batch: offsets must hold len(docs) + 1 entries")
+    if specials is not None:
+        check_specials(specials)
     arr = _merges_to_arr(merges)
     n = ctypes.c_size_t(0)
     bo = ctypes.POINTER(ctypes.c_uint64)()
     try:
-        p = L.bpe_decode_docs(ids.ctypes.data_as(ctypes.c_void_p), ids.size, off.ctypes.data_as(ctypes.c_void_p),
-                              off.size - 1, arr, int(device), ctypes.byref(n), ctypes.byref(bo))
+        if specials is not None:
+            sp = _Specials(specials)
+            p = L.bpe_decode_docs_special(ids.ctypes.data_as(ctypes.c_void_p), ids.size,
+                                          off.ctypes.data_as(ctypes.c_void_p), off.size - 1, arr, sp.ref, int(device),
+                                          ctypes.byref(n), ctypes.byref(bo))
+        else:
+            p = L.bpe_decode_docs(ids.ctypes.data_as(ctypes.c_void_p), ids.size, off.ctypes.data_as(ctypes.c_void_p),
+                                  off.size - 1, arr, int(device), ctypes.byref(n), ctypes.byref(bo))
     finally:
         L.dyn_arr_free(arr)
     if not p:
@@ -407,11 +490,19 @@ class Engine:
         _lib.check(self.L.bpe_gpu_encode_docs(self.ctx, off.ctypes.data_as(ctypes.c_void_p), off.size - 1,
                                               m.ctypes.data_as(ctypes.c_void_p), m.size // 2), "encode_docs")
 
-    def split(self, rule="words"):
+    def split(self, rule="words", specials=None):
         """split the resident bytes into pieces on the device (rule: a preset
         name, "lines", "words" or "gpt2", or a (cls, brk) pair, see split_rule); the offsets stay in HBM for
-        encode_split().  Returns the number of pieces."""
+        encode_split().  With specials (a list of bytes-like objects, see check_specials) every occurrence of
+        one is a piece of its own (bpe_gpu_split_special); they last as long as the offsets, and a split
+        without them forgets them.  Returns the number of pieces."""
         nd = ctypes.c_size_t(0)
+        if specials is not None:
+            check_specials(specials)  # (before any launch)
+            sp = _Specials(specials)
+            preset, pc, pb, keep = _rule_args(rule)
+            _lib.check(self.L.bpe_gpu_split_special(self.ctx, preset, pc, pb, sp.ref, ctypes.byref(nd)), "split")
+            return nd.value
         if isinstance(rule, str) and rule == "gpt2":  # no tables: the preset call (bpe_gpu_split_preset)
             _lib.check(self.L.bpe_gpu_split_preset(self.ctx, SPLIT_PRESETS[rule], ctypes.byref(nd)), "split")
             return nd.value
@@ -429,9 +520,29 @@ class Engine:
                                                       ctypes.byref(n)), "fetch_split_offsets")
         return out
 
+    SPLIT_SPECIAL_INFO = ("specials", "matches", "find_passes", "match_capacity")
+
+    def split_special_info(self):
+        """counters of the last split's specials (bpe_gpu_split_special_info; zeros after a split without)"""
+        out = np.zeros(4, dtype=np.uint64)
+        _lib.check(self.L.bpe_gpu_split_special_info(self.ctx, out.ctypes.data_as(ctypes.c_void_p)), "split_special_info")
+        return {k: int(out[i]) for i, k in enumerate(self.SPLIT_SPECIAL_INFO)}
+
+    def special_pieces(self):
+        """the special pieces of the last split in order: (piece index uint64, index of its special uint32)"""
+        n = ctypes.c_size_t(0)
+        _lib.check(self.L.bpe_gpu_fetch_special_pieces(self.ctx, None, None, 0, ctypes.byref(n)), "fetch_special_pieces")
+        piece = np.zeros(max(n.value, 1), dtype=np.uint64)
+        index = np.zeros(max(n.value, 1), dtype=np.uint32)
+        vp = ctypes.c_void_p
+        _lib.check(self.L.bpe_gpu_fetch_special_pieces(self.ctx, piece.ctypes.data_as(vp), index.ctypes.data_as(vp),
+                                                       n.value, ctypes.byref(n)), "fetch_special_pieces")
+        return piece[: n.value], index[: n.value]
+
     def encode_split(self, merges):
         """encode_docs over the last split's resident offsets (bpe_gpu_encode_split);
-        then ids(), doc_offsets(), docs_info() as after encode_docs"""
+        then ids(), doc_offsets(), docs_info() as after encode_docs.  After a split with specials
+        every special piece holds the one id 256 + len(merges) + j."""
         m = np.ascontiguousarray(merges, dtype=np.uint32).reshape(-1)
         _lib.check(self.L.bpe_gpu_encode_split(self.ctx, m.ctypes.data_as(ctypes.c_void_p), m.size // 2), "encode_split")
 
@@ -491,8 +602,9 @@ class Engine:
         _lib.check(self.L.bpe_gpu_docs_info(self.ctx, out.ctypes.data_as(ctypes.c_void_p)), "docs_info")
         return {k: int(out[i]) for i, k in enumerate(self.DOCS_INFO)}
 
-    def decode_docs(self, ids, offsets, merges):
-        """(bytes, byte offsets) of ids held as documents (bpe_gpu_decode_docs)"""
+    def decode_docs(self, ids, offsets, merges, specials=None):
+        """(bytes, byte offsets) of ids held as documents (bpe_gpu_decode_docs); with specials (see split) the
+        id 256 + len(merges) + j is specials[j] (bpe_gpu_decode_docs_special)"""
         ids = np.ascontiguousarray(ids, dtype=np.uint32)
         off = _doc_offsets(offsets)
         if off.size < 1:
@@ -502,11 +614,15 @@ class Engine:
         vp = ctypes.c_void_p
         args = (self.ctx, ids.ctypes.data_as(vp), ids.size, off.ctypes.data_as(vp), off.size - 1, m.ctypes.data_as(vp),
                 m.size // 2)
-        _lib.check(self.L.bpe_gpu_decode_docs(*args, None, 0, ctypes.byref(n), None), "decode_docs")
+        fn = self.L.bpe_gpu_decode_docs
+        if specials is not None:
+            check_specials(specials)
+            sp = _Specials(specials)
+            fn, args = self.L.bpe_gpu_decode_docs_special, args + (sp.ref,)
+        _lib.check(fn(*args, None, 0, ctypes.byref(n), None), "decode_docs")
         out = np.zeros(max(n.value, 1), dtype=np.uint8)
         bo = np.zeros(off.size, dtype=np.uint64)
-        _lib.check(self.L.bpe_gpu_decode_docs(*args, out.ctypes.data_as(vp), out.size, ctypes.byref(n),
-                                              bo.ctypes.data_as(vp)), "decode_docs")
+        _lib.check(fn(*args, out.ctypes.data_as(vp), out.size, ctypes.byref(n), bo.ctypes.data_as(vp)), "decode_docs")
         return out[: n.value].tobytes(), bo
 
     def merges(self):

@@ -28,6 +28,10 @@
 #include "encode_docs.hip"
 #include "split.hip"
 #include "train_split.hip"
+#include "special.hip"
+
+// (bpe_ex.h, src/bpe_special.c: the host definition of a valid set)
+extern "C" int bpe_specials_check(const bpe_gpu_specials *specials, char *msg, size_t msg_cap);
 
 using namespace bpeamd;
 
@@ -303,6 +307,14 @@ struct bpe_gpu_ctx {
     uint64_t split_n = 0;
     uint64_t *d_split = nullptr;
     size_t split_cap = 0;  // entries d_split holds
+    // the specials of the last bpe_gpu_split_special (sp_S == 0: a split without) and its special pieces in
+    // order, (piece << 8 | j) each, in a buffer of its own like d_split.  Valid while split_ready; every split
+    // sets them anew.
+    uint32_t sp_S = 0;
+    uint64_t sp_M = 0;
+    unsigned long long *d_sp_pieces = nullptr;
+    size_t sp_cap = 0;  // entries d_sp_pieces holds
+    uint64_t sp_info[4] = {};
     // the last bpe_gpu_train_split over those offsets: its merges (host), bpe_gpu_train_split_info's fields and
     // the piece table (scratch slots 22-24).  Valid while split_ready: whatever drops the offsets drops these.
     bool ts_ready = false;
@@ -342,9 +354,11 @@ struct bpe_gpu_ctx {
     // of bpe_gpu_split (start table, start masks, wave counts + their scan, scan temporaries; 12-15),
     // of bpe_gpu_train_split (piece table 16-17, control words 18, entry records 19-25, scan and sort
     // temporaries 26, tokens and their entries 27-30, rewrite flags and scans 31-34, pair table 35-37),
-    // and the pinned staging of file loads
-    void *dscr[38] = {};
-    size_t dscr_cap[38] = {};
+    // of the special tokens (the set 38, cover bitmap 39, match list and its sorted copy 40-41, sort and scan
+    // temporaries 42, control words 43, the post-pass's first ids / removed ids / their scan 44-46, the
+    // decoder's bytes and offsets 47-48), and the pinned staging of file loads
+    void *dscr[49] = {};
+    size_t dscr_cap[49] = {};
     std::vector<uint32_t> ew_stage;  // host image of the window encoder's tables (outlives the upload)
     uint8_t *stage[2] = {};
     hipEvent_t stage_ev[2] = {};
@@ -2516,6 +2530,7 @@ void bpe_gpu_destroy(bpe_gpu_ctx *c) {
     if (c->d_pres) hipFree(c->d_pres);
     if (c->d_enc_pairs) hipFree(c->d_enc_pairs);
     if (c->d_split) hipFree(c->d_split);
+    if (c->d_sp_pieces) hipFree(c->d_sp_pieces);
     for (void *p : c->dscr)
         if (p) (void)hipFree(p);
     for (int k = 0; k < 2; k++) {
@@ -2911,20 +2926,41 @@ void dec_elen_host(const uint32_t *pairs, uint32_t nm, uint64_t *elen) {
     }
 }
 
-int bpe_gpu_decode(bpe_gpu_ctx *c, const uint32_t *ids, size_t len, const uint32_t *pairs, size_t n_merges,
-                   uint8_t *out, size_t cap, size_t *out_len) {
+// The body of bpe_gpu_decode (sp == nullptr or an empty set: its launches and nothing else) and of
+// bpe_gpu_decode_docs_special: the ids V0 .. V0 + S - 1 past the merge list's are the (checked) specials, whose
+// lengths follow the merge list's in elen and whose bytes k_sp_dec_expand copies.
+static int decode_run(bpe_gpu_ctx *c, const uint32_t *ids, size_t len, const uint32_t *pairs, size_t n_merges,
+                      const bpe_gpu_specials *sp, uint8_t *out, size_t cap, size_t *out_len) {
     if (!c || !out_len || (!ids && len) || (!pairs && n_merges)) return BPE_GPU_EINVAL;
     if (n_merges > 0xFFFFFEFFull) return fail(BPE_GPU_ERANGE, "merge list too long");
+    const uint32_t S = sp ? (uint32_t)sp->count : 0u;
+    if (S && n_merges + 256 + S > 0xFFFFFFFFull) return fail(BPE_GPU_ERANGE, "merge list too long for the specials' ids");
     HIPCHK(hipSetDevice(c->dev));
     // all on the device: expansion lengths per id (k_dec_elen), their prefix
     // sum over the ids (rocprim scan), the byte gather (k_dec_expand)
-    const uint32_t V = (uint32_t)(256 + n_merges);
+    const uint32_t V0 = (uint32_t)(256 + n_merges), V = V0 + S;
     int r;
     void *p[7];
     if ((r = dscratch(c, 0, std::max<size_t>(len, 1) * 4, &p[0])) || (r = dscratch(c, 1, std::max<size_t>(n_merges, 1) * 8, &p[1])) ||
         (r = dscratch(c, 2, (size_t)V * 8, &p[2])) || (r = dscratch(c, 3, (len + 1) * 8, &p[3])) ||
         (r = dscratch(c, 6, 64, &p[6])))
         return r;
+    uint8_t *d_sp = nullptr;
+    uint32_t *d_soff = nullptr;
+    std::vector<uint64_t> sp_elen(S);
+    std::vector<uint32_t> sp_off(S + 1, 0);
+    for (uint32_t j = 0; j < S; j++) {
+        sp_elen[j] = sp->len[j];
+        sp_off[j + 1] = sp_off[j] + sp->len[j];
+    }
+    if (S) {
+        void *a, *b;
+        if ((r = dscratch(c, 47, sp_off[S], &a)) || (r = dscratch(c, 48, (S + 1) * 4, &b))) return r;
+        d_sp = (uint8_t *)a;
+        d_soff = (uint32_t *)b;
+        HIPCHK(hipMemcpyAsync(d_sp, sp->bytes, sp_off[S], hipMemcpyHostToDevice, c->st));
+        HIPCHK(hipMemcpyAsync(d_soff, sp_off.data(), (S + 1) * 4, hipMemcpyHostToDevice, c->st));
+    }
     uint32_t *d_ids = (uint32_t *)p[0], *d_pairs = (uint32_t *)p[1], *d_err = (uint32_t *)p[6];
     uint64_t *d_elen = (uint64_t *)p[2], *d_off = (uint64_t *)p[3];
     HIPCHK(hipMemsetAsync(d_err, 0, 8, c->st));
@@ -2937,12 +2973,13 @@ int bpe_gpu_decode(bpe_gpu_ctx *c, const uint32_t *ids, size_t len, const uint32
         HIPCHK(hipMemcpyAsync(&unf, d_err + 1, 4, hipMemcpyDeviceToHost, c->st));
         HIPCHK(hipStreamSynchronize(c->st));
         if (unf) {  // deep merge chains: the rest in one host pass (rank order + DFS for the others)
-            std::vector<uint64_t> he(V);
+            std::vector<uint64_t> he(V0);
             dec_elen_host(pairs, (uint32_t)n_merges, he.data());
-            HIPCHK(hipMemcpyAsync(d_elen, he.data(), (size_t)V * 8, hipMemcpyHostToDevice, c->st));
+            HIPCHK(hipMemcpyAsync(d_elen, he.data(), (size_t)V0 * 8, hipMemcpyHostToDevice, c->st));
             HIPCHK(hipStreamSynchronize(c->st));
         }
     }
+    if (S) HIPCHK(hipMemcpyAsync(d_elen + V0, sp_elen.data(), (size_t)S * 8, hipMemcpyHostToDevice, c->st));
     if (len) k_dec_check<<<1024, 256, 0, c->st>>>(d_ids, len, V, d_elen, d_err);
     HIPCHK(hipGetLastError());
     auto lens = rocprim::make_transform_iterator(rocprim::make_counting_iterator<uint64_t>(0),
@@ -2963,11 +3000,17 @@ int bpe_gpu_decode(bpe_gpu_ctx *c, const uint32_t *ids, size_t len, const uint32
     if (cap < total) return fail(BPE_GPU_EINVAL, "decode: output buffer too small");
     if (len == 0 || total == 0) return 0;
     if ((r = dscratch(c, 5, total, &p[5]))) return r;
-    k_dec_expand<<<1024, 256, 0, c->st>>>(d_ids, len, d_pairs, d_elen, d_off, (uint8_t *)p[5]);
+    if (S) k_sp_dec_expand<<<1024, 256, 0, c->st>>>(d_ids, len, d_pairs, d_elen, d_off, V0, d_sp, d_soff, (uint8_t *)p[5]);
+    else k_dec_expand<<<1024, 256, 0, c->st>>>(d_ids, len, d_pairs, d_elen, d_off, (uint8_t *)p[5]);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out, p[5], total, hipMemcpyDeviceToHost, c->st));
     HIPCHK(hipStreamSynchronize(c->st));
     return 0;
+}
+
+int bpe_gpu_decode(bpe_gpu_ctx *c, const uint32_t *ids, size_t len, const uint32_t *pairs, size_t n_merges,
+                   uint8_t *out, size_t cap, size_t *out_len) {
+    return decode_run(c, ids, len, pairs, n_merges, nullptr, out, cap, out_len);
 }
 
 // Stream the first `size` bytes of fd (positional reads from offset 0; the
@@ -3182,6 +3225,11 @@ int bpe_gpu_trim(bpe_gpu_ctx *c) {
     if (c->d_split) (void)hipFree(c->d_split);
     c->d_split = nullptr;
     c->split_cap = 0;
+    if (c->d_sp_pieces) (void)hipFree(c->d_sp_pieces);
+    c->d_sp_pieces = nullptr;
+    c->sp_cap = 0;
+    c->sp_S = 0;
+    c->sp_M = 0;
     for (int k = 0; k < (int)(sizeof c->dscr / sizeof c->dscr[0]); k++) {
         if (c->dscr[k]) (void)hipFree(c->dscr[k]);
         c->dscr[k] = nullptr;
@@ -3421,12 +3469,70 @@ int bpe_gpu_split_info(uint64_t *out4) {
     return 0;
 }
 
+// workgroups of the per-match / per-id kernels of special.hip (they stride)
+static uint32_t sx_grid(uint64_t items) {
+    return (uint32_t)std::min<uint64_t>(std::max<uint64_t>((items + SX_T - 1) / SX_T, 1), SX_GRID);
+}
+
+// The special passes of a split, between the marking kernel and the count scan (special.hip): find, and when
+// there are matches patch, recount and sort.  *M matches, *sorted their list by start (scratch slot 41).
+static int sp_mark(bpe_gpu_ctx *c, const SpSet *sp, bool gpt2, uint64_t n, uint64_t ntiles, uint32_t grid, uint16_t *mask,
+                   uint32_t *wcnt, uint32_t *M, unsigned long long **sorted, uint64_t *info) {
+    int r;
+    void *pset, *pcov, *pctl, *plist = nullptr, *psort, *tmp;
+    const size_t cov_bytes = ntiles * SP_T * 2;  // a bit per byte of the whole tiles
+    if ((r = dscratch(c, 38, sizeof(SpSet), &pset)) || (r = dscratch(c, 39, cov_bytes, &pcov)) || (r = dscratch(c, 43, 64, &pctl)))
+        return r;
+    uint32_t *ctl = (uint32_t *)pctl;
+    HIPCHK(hipMemcpyAsync(pset, sp, sizeof(SpSet), hipMemcpyHostToDevice, c->st));
+    HIPCHK(hipMemsetAsync(pcov, 0, cov_bytes, c->st));
+    // room for a match every 256 bytes; a text with more runs the pass again with the room it counted
+    uint64_t cap = n / 256 + 1024;
+    uint32_t found = 0;
+    for (int pass = 1;; pass++) {
+        if ((r = dscratch(c, 40, cap * 8, &plist))) return r;
+        HIPCHK(hipMemsetAsync(ctl, 0, 64, c->st));
+        k_sp_find<<<grid, SP_T, 0, c->st>>>(c->h.bytes, n, ntiles, (const SpSet *)pset, (uint32_t *)pcov,
+                                            (unsigned long long *)plist, (uint32_t)std::min<uint64_t>(cap, 0xFFFFFFFFull), ctl);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(&found, ctl, 4, hipMemcpyDeviceToHost, c->st));
+        HIPCHK(hipStreamSynchronize(c->st));
+        info[2] = (uint64_t)pass;
+        if (found <= cap) break;
+        if (pass == 2) return fail(BPE_GPU_EINTERNAL, "split_special: the second find pass counted more matches than the first");
+        cap = found;
+    }
+    info[1] = found;
+    info[3] = cap;
+    *M = found;
+    *sorted = nullptr;
+    if (!found) return 0;
+    k_sp_patch<<<sx_grid(found), SX_T, 0, c->st>>>(c->h.bytes, n, (const unsigned long long *)plist, found, (const SpSet *)pset,
+                                                  (const uint32_t *)pcov, (uint32_t *)mask, gpt2 ? 1 : 0);
+    HIPCHK(hipGetLastError());
+    k_sp_recount<<<grid, SP_T, 0, c->st>>>(mask, ntiles, wcnt);
+    HIPCHK(hipGetLastError());
+    if ((r = dscratch(c, 41, (size_t)found * 8, &psort))) return r;
+    size_t tb = 0;
+    HIPCHK(rocprim::radix_sort_keys(nullptr, tb, (unsigned long long *)plist, (unsigned long long *)psort, found, 8, 40, c->st));
+    if ((r = dscratch(c, 42, tb, &tmp))) return r;
+    HIPCHK(rocprim::radix_sort_keys(tmp, tb, (unsigned long long *)plist, (unsigned long long *)psort, found, 8, 40, c->st));
+    *sorted = (unsigned long long *)psort;
+    return 0;
+}
+
 // the body of bpe_gpu_split (R: the tables) and of bpe_gpu_split_preset's BPE_SPLIT_GPT2 (R == nullptr): all but
-// the marking launch is one code, so the offsets and their lifetime are the same whichever kernel marked the starts
-static int split_run(bpe_gpu_ctx *c, const SplitRule *R, size_t *ndocs) {
+// the marking launch is one code, so the offsets and their lifetime are the same whichever kernel marked the starts.
+// sp: the specials of bpe_gpu_split_special (nullptr: none, and nothing but the launches below runs)
+static int split_run(bpe_gpu_ctx *c, const SplitRule *R, size_t *ndocs, const SpSet *sp = nullptr) {
     HIPCHK(hipSetDevice(c->dev));
     c->split_ready = false;
     c->ts_ready = false;  // bpe_gpu_train_split's results describe the offsets replaced here
+    c->sp_S = 0;          // ... and so do the specials and their pieces
+    c->sp_M = 0;
+    uint64_t sp_info[4] = {sp ? sp->S : 0u, 0, 0, 0};
+    uint32_t sp_M = 0;
+    unsigned long long *sp_sorted = nullptr;
     const uint64_t n = c->n0, ntiles = (n + SP_TILE - 1) / SP_TILE, nwt = ntiles * (SP_T / 64);
     unsigned long long total = 0;
     uint16_t *mask = nullptr;
@@ -3451,6 +3557,7 @@ static int split_run(bpe_gpu_ctx *c, const SplitRule *R, size_t *ndocs) {
             k_split_mark_gpt2<<<grid, SP_T, 0, c->st>>>(c->h.bytes, n, ntiles, mask, wcnt);
         }
         HIPCHK(hipGetLastError());
+        if (sp && (r = sp_mark(c, sp, R == nullptr, n, ntiles, grid, mask, wcnt, &sp_M, &sp_sorted, sp_info))) return r;
         size_t tb = 0;
         HIPCHK(rocprim::exclusive_scan(nullptr, tb, wcnt, woff, 0ull, nwt + 1, rocprim::plus<unsigned long long>(), c->st));
         if ((r = dscratch(c, 15, tb, &tmp))) return r;
@@ -3479,7 +3586,30 @@ static int split_run(bpe_gpu_ctx *c, const SplitRule *R, size_t *ndocs) {
     } else {
         HIPCHK(hipMemsetAsync(c->d_split, 0, 8, c->st));
     }
+    if (sp_M) {  // the matches' starts as piece indices: the list that stays
+        if (c->sp_cap < sp_M) {
+            HIPCHK(hipStreamSynchronize(c->st));
+            if (c->d_sp_pieces) (void)hipFree(c->d_sp_pieces);
+            c->d_sp_pieces = nullptr;
+            c->sp_cap = 0;
+            hipError_t e = hipMalloc(&c->d_sp_pieces, (size_t)sp_M * 8);
+            if (e != hipSuccess) {
+                (void)hipGetLastError();
+                return fail(BPE_GPU_ENOMEM, "split_special: hipMalloc of the special pieces", e);
+            }
+            c->sp_cap = sp_M;
+        }
+        uint32_t *ctl = (uint32_t *)c->dscr[43], bad = 0;
+        k_sp_pieces<<<sx_grid(sp_M), SX_T, 0, c->st>>>(sp_sorted, sp_M, c->d_split, total, c->d_sp_pieces, ctl + 1);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(&bad, ctl + 1, 4, hipMemcpyDeviceToHost, c->st));
+        HIPCHK(hipStreamSynchronize(c->st));
+        if (bad) return fail(BPE_GPU_EINTERNAL, "split_special: a match does not start a piece");
+    }
     HIPCHK(hipStreamSynchronize(c->st));
+    c->sp_S = sp ? sp->S : 0u;
+    c->sp_M = sp_M;
+    memcpy(c->sp_info, sp_info, sizeof sp_info);
     c->split_n = total;
     c->split_ready = true;
     *ndocs = (size_t)total;
@@ -3510,6 +3640,81 @@ int bpe_gpu_split_preset(bpe_gpu_ctx *c, int preset, size_t *ndocs) {
     return r ? r : bpe_gpu_split(c, cls, brk, ndocs);
 }
 
+int bpe_gpu_split_special(bpe_gpu_ctx *c, int preset, const uint8_t *cls, const uint16_t *brk,
+                          const bpe_gpu_specials *specials, size_t *ndocs) {
+    if (!c || !ndocs) return BPE_GPU_EINVAL;
+    if (preset < 0 && (!cls || !brk)) return fail(BPE_GPU_EINVAL, "split_special: no preset and no tables");
+    if (preset >= 0 && preset != BPE_SPLIT_LINES && preset != BPE_SPLIT_WORDS && preset != BPE_SPLIT_GPT2)
+        return fail(BPE_GPU_EINVAL, "split_special: no such preset");
+    char msg[400];
+    if (bpe_specials_check(specials, msg, sizeof msg)) return fail(BPE_GPU_EINVAL, msg);
+    if (!c->loaded) return fail(BPE_GPU_ESTATE, "split before load");
+    const size_t S = specials ? specials->count : 0;
+    if (S == 0) return preset < 0 ? bpe_gpu_split(c, cls, brk, ndocs) : bpe_gpu_split_preset(c, preset, ndocs);
+    // the set as the device reads it: in lexicographic order (no special is a prefix of another, so the first
+    // difference decides), with the first-byte set
+    std::vector<SpSet> hs(1);
+    SpSet &H = hs[0];
+    memset(&H, 0, sizeof H);
+    std::vector<size_t> off(S + 1, 0);
+    for (size_t j = 0; j < S; j++) off[j + 1] = off[j] + specials->len[j];
+    std::vector<uint32_t> order(S);
+    for (size_t j = 0; j < S; j++) order[j] = (uint32_t)j;
+    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
+        const int d = memcmp(specials->bytes + off[a], specials->bytes + off[b], std::min(specials->len[a], specials->len[b]));
+        return d ? d < 0 : specials->len[a] < specials->len[b];
+    });
+    for (size_t k = 0; k < S; k++) {
+        const uint32_t j = order[k], L = specials->len[j];
+        memcpy(H.txt + k * SX_LEN, specials->bytes + off[j], L);
+        H.len[k] = (uint8_t)(L - 1);
+        H.idx[k] = (uint8_t)j;
+        H.lenj[j] = (uint8_t)(L - 1);
+        const uint8_t b = specials->bytes[off[j]];
+        H.first[b >> 5] |= 1u << (b & 31);
+    }
+    H.S = (uint32_t)S;
+    SplitRule R;
+    if (preset == BPE_SPLIT_GPT2) return split_run(c, nullptr, ndocs, &H);
+    if (preset >= 0) {
+        uint8_t pc[256];
+        const int r = bpe_gpu_split_rule(preset, pc, R.brk);
+        if (r) return r;
+        memcpy(R.cls, pc, 256);
+    } else {
+        for (int b = 0; b < 256; b++)
+            if ((R.cls[b] = cls[b]) > 15) return fail(BPE_GPU_EINVAL, "split: a class above 15");
+        memcpy(R.brk, brk, sizeof R.brk);
+    }
+    return split_run(c, &R, ndocs, &H);
+}
+
+int bpe_gpu_split_special_info(bpe_gpu_ctx *c, uint64_t *out4) {
+    if (!c || !out4) return BPE_GPU_EINVAL;
+    if (!c->loaded || !c->split_ready) return fail(BPE_GPU_ESTATE, "no split: split first");
+    memset(out4, 0, 4 * sizeof(uint64_t));
+    if (c->sp_S) memcpy(out4, c->sp_info, sizeof c->sp_info);
+    return 0;
+}
+
+int bpe_gpu_fetch_special_pieces(bpe_gpu_ctx *c, uint64_t *piece, uint32_t *index, size_t cap, size_t *count) {
+    if (!c || !count) return BPE_GPU_EINVAL;
+    if (!c->loaded || !c->split_ready) return fail(BPE_GPU_ESTATE, "no special pieces: split first");
+    HIPCHK(hipSetDevice(c->dev));
+    const uint64_t M = c->sp_S ? c->sp_M : 0;
+    *count = (size_t)M;
+    const size_t k = std::min<size_t>(cap, (size_t)M);
+    if (!k || (!piece && !index)) return 0;
+    std::vector<unsigned long long> h(k);
+    const int r = d2h_staged(c, h.data(), c->d_sp_pieces, k * 8);
+    if (r) return r;
+    for (size_t m = 0; m < k; m++) {
+        if (piece) piece[m] = h[m] >> 8;
+        if (index) index[m] = (uint32_t)(h[m] & 0xFFull);
+    }
+    return 0;
+}
+
 int bpe_gpu_fetch_split_offsets(bpe_gpu_ctx *c, uint64_t *out, size_t cap, size_t *count) {
     if (!c || !count) return BPE_GPU_EINVAL;
     if (!c->loaded || !c->split_ready) return fail(BPE_GPU_ESTATE, "no split offsets: split first");
@@ -3525,7 +3730,46 @@ int bpe_gpu_encode_split(bpe_gpu_ctx *c, const uint32_t *pairs, size_t n_merges)
     if (!c->loaded) return fail(BPE_GPU_ESTATE, "encode before load");
     if (!c->split_ready) return fail(BPE_GPU_ESTATE, "encode_split: no split of the loaded bytes");
     if (n_merges > 0xFFFFFEFFull) return fail(BPE_GPU_ERANGE, "merge list too long");
-    return encode_docs_run(c, nullptr, c->split_n, pairs, n_merges, now_ms());
+    const uint64_t M = c->sp_S ? c->sp_M : 0;
+    if (M && n_merges + 256 + c->sp_S > 0xFFFFFFFFull) return fail(BPE_GPU_ERANGE, "merge list too long for the specials' ids");
+    int r = encode_docs_run(c, nullptr, c->split_n, pairs, n_merges, now_ms());
+    if (r || !M) return r;
+    // The post-pass (special.hip): whichever path left ids_out / d_idoff, every special piece keeps one id,
+    // 256 + n_merges + j, and the ids and offsets after it move down.
+    const double t0 = now_ms();
+    const uint64_t len = c->ids_len, ndocs = c->split_n;
+    void *pist, *prem, *prs, *tmp;
+    if ((r = dscratch(c, 44, M * 8, &pist)) || (r = dscratch(c, 45, (M + 1) * 8, &prem)) || (r = dscratch(c, 46, (M + 1) * 8, &prs)))
+        return r;
+    uint64_t *ist = (uint64_t *)pist, *rem = (uint64_t *)prem, *rsum = (uint64_t *)prs;
+    k_sp_idlen<<<sx_grid(M + 1), SX_T, 0, c->st>>>(c->d_sp_pieces, (uint32_t)M, c->d_idoff, ist, rem);
+    HIPCHK(hipGetLastError());
+    size_t tb = 0;
+    HIPCHK(rocprim::exclusive_scan(nullptr, tb, rem, rsum, (uint64_t)0, M + 1, rocprim::plus<uint64_t>(), c->st));
+    if ((r = dscratch(c, 42, tb, &tmp))) return r;
+    HIPCHK(rocprim::exclusive_scan(tmp, tb, rem, rsum, (uint64_t)0, M + 1, rocprim::plus<uint64_t>(), c->st));
+    uint64_t removed = 0;
+    HIPCHK(hipMemcpyAsync(&removed, rsum + M, 8, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipStreamSynchronize(c->st));
+    if (removed > len || len - removed < M) return fail(BPE_GPU_EINTERNAL, "encode_split: the special pieces hold more ids than there are");
+    uint32_t *ids2;
+    uint64_t *idoff2;
+    if ((r = dalloc(c, &ids2, len - removed, false)) || (r = dalloc(c, &idoff2, ndocs + 1, false))) return r;
+    k_sp_ids<<<sx_grid(len), SX_T, 0, c->st>>>(c->h.ids_out, len, c->d_sp_pieces, (uint32_t)M, ist, rsum,
+                                              (uint32_t)(256 + n_merges), ids2);
+    HIPCHK(hipGetLastError());
+    k_sp_idoff<<<sx_grid(ndocs + 1), SX_T, 0, c->st>>>(c->d_idoff, ndocs, c->d_sp_pieces, (uint32_t)M, rsum, idoff2);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->st));
+    c->h.ids_out = ids2;
+    c->d_idoff = idoff2;
+    c->ids_len = len - removed;
+    const double ms = now_ms() - t0;
+    c->stats.n_out = c->ids_len;
+    c->stats.occurrences = c->n0 - std::min<uint64_t>(c->n0, c->ids_len);
+    c->stats.ms_train += ms;
+    c->stats.ms_total += ms;
+    return 0;
 }
 
 // ------------------------------------------------ training on the pieces (train_split.hip)
@@ -3570,7 +3814,7 @@ static int ts_piece_table(bpe_gpu_ctx *c, uint32_t *ctl, uint64_t *E, uint64_t *
     }
     *slots = S;
     *nlong = hc[TSC_LONG];
-    const uint64_t ne = (uint64_t)hc[TSC_LONG] + hc[TSC_CLAIMED];
+    uint64_t ne = (uint64_t)hc[TSC_LONG] + hc[TSC_CLAIMED];
     if (ne == 0 || ne > P) return fail(BPE_GPU_EINTERNAL, "train_split: entry count out of range");
     void *k0, *v0, *k1, *v1, *est, *elen, *eoff, *tmp;
     if ((r = dscratch(c, 19, ne * 4, &k0)) || (r = dscratch(c, 20, ne * 4, &v0)) || (r = dscratch(c, 21, ne * 4, &k1)) ||
@@ -3584,19 +3828,29 @@ static int ts_piece_table(bpe_gpu_ctx *c, uint32_t *ctl, uint64_t *E, uint64_t *
         k_ts_collect_long<<<ts_grid(P), TS_T, 0, c->st>>>(off, P, ctl, (uint32_t *)k0, (uint32_t *)v0, ne);
         HIPCHK(hipGetLastError());
     }
+    // After a split with specials their pieces are no part of the corpus: each special is at most one record
+    // (it fits TS_DEDUP_MAX), whose key k_sp_drop sets to 0xFFFFFFFF, so that it sorts past the entries.
+    const uint64_t nrec = ne;
+    if (c->sp_S && c->sp_M) {
+        k_sp_drop<<<sx_grid(nrec), SX_T, 0, c->st>>>((uint32_t *)k0, nrec, c->d_sp_pieces, (uint32_t)c->sp_M, ctl + 8);
+        HIPCHK(hipGetLastError());
+        if ((r = ts_read_ctl(c, ctl, hc))) return r;
+        if (hc[8] > c->sp_S || hc[8] > nrec) return fail(BPE_GPU_EINTERNAL, "train_split: more special records than specials");
+        ne = nrec - hc[8];
+    }
     size_t tb = 0, tb2 = 0;
-    HIPCHK(rocprim::radix_sort_pairs(nullptr, tb, (uint32_t *)k0, (uint32_t *)k1, (uint32_t *)v0, (uint32_t *)v1, ne, 0, 32, c->st));
+    HIPCHK(rocprim::radix_sort_pairs(nullptr, tb, (uint32_t *)k0, (uint32_t *)k1, (uint32_t *)v0, (uint32_t *)v1, nrec, 0, 32, c->st));
     HIPCHK(rocprim::exclusive_scan(nullptr, tb2, (uint32_t *)elen, (uint32_t *)eoff, 0u, ne + 1, rocprim::plus<uint32_t>(), c->st));
     tb = std::max(tb, tb2);
     if ((r = dscratch(c, 26, tb, &tmp))) return r;
-    HIPCHK(rocprim::radix_sort_pairs(tmp, tb, (uint32_t *)k0, (uint32_t *)k1, (uint32_t *)v0, (uint32_t *)v1, ne, 0, 32, c->st));
+    HIPCHK(rocprim::radix_sort_pairs(tmp, tb, (uint32_t *)k0, (uint32_t *)k1, (uint32_t *)v0, (uint32_t *)v1, nrec, 0, 32, c->st));
     k_ts_entries<<<(uint32_t)((ne + TS_T) / TS_T), TS_T, 0, c->st>>>(off, (const uint32_t *)k1, ne, (uint64_t *)est, (uint32_t *)elen);
     HIPCHK(hipGetLastError());
     HIPCHK(rocprim::exclusive_scan(tmp, tb, (uint32_t *)elen, (uint32_t *)eoff, 0u, ne + 1, rocprim::plus<uint32_t>(), c->st));
     uint32_t total = 0;
     HIPCHK(hipMemcpyAsync(&total, (uint32_t *)eoff + ne, 4, hipMemcpyDeviceToHost, c->st));
     if ((r = ts_read_ctl(c, ctl, hc))) return r;
-    if (hc[TSC_APPEND] != ne) return fail(BPE_GPU_EINTERNAL, "train_split: entry records do not match their count");
+    if (hc[TSC_APPEND] != nrec) return fail(BPE_GPU_EINTERNAL, "train_split: entry records do not match their count");
     if (total < ne || total > c->n0) return fail(BPE_GPU_EINTERNAL, "train_split: entry bytes out of range");
     *E = ne;
     *T = total;
@@ -3763,15 +4017,16 @@ int bpe_gpu_docs_info(bpe_gpu_ctx *c, uint64_t *out8) {
     return 0;
 }
 
-int bpe_gpu_decode_docs(bpe_gpu_ctx *c, const uint32_t *ids, size_t len, const uint64_t *id_off, size_t ndocs,
-                        const uint32_t *pairs, size_t n_merges, uint8_t *out, size_t cap, size_t *out_len,
-                        uint64_t *byte_off) {
+// the body of bpe_gpu_decode_docs (sp == nullptr) and of bpe_gpu_decode_docs_special
+static int decode_docs_run(bpe_gpu_ctx *c, const uint32_t *ids, size_t len, const uint64_t *id_off, size_t ndocs,
+                           const uint32_t *pairs, size_t n_merges, const bpe_gpu_specials *sp, uint8_t *out, size_t cap,
+                           size_t *out_len, uint64_t *byte_off) {
     if (!c || !out_len || !id_off || (!ids && len) || (!pairs && n_merges)) return BPE_GPU_EINVAL;
     if (id_off[0] != 0 || id_off[ndocs] != len) return fail(BPE_GPU_EINVAL, "decode_docs: offsets must run from 0 to len");
     for (size_t d = 0; d < ndocs; d++)
         if (id_off[d] > id_off[d + 1]) return fail(BPE_GPU_EINVAL, "decode_docs: offsets decrease");
     int r;
-    if ((r = bpe_gpu_decode(c, ids, len, pairs, n_merges, out, cap, out_len))) return r;
+    if ((r = decode_run(c, ids, len, pairs, n_merges, sp, out, cap, out_len))) return r;
     if (!byte_off) return 0;
     // byte_off[d] = the ids' expansion-length prefix sum (left in scratch slot 3 by bpe_gpu_decode) at id_off[d]
     void *d_idx, *d_out;
@@ -3783,6 +4038,25 @@ int bpe_gpu_decode_docs(bpe_gpu_ctx *c, const uint32_t *ids, size_t len, const u
     HIPCHK(hipMemcpyAsync(byte_off, d_out, (ndocs + 1) * 8, hipMemcpyDeviceToHost, c->st));
     HIPCHK(hipStreamSynchronize(c->st));
     return 0;
+}
+
+int bpe_gpu_decode_docs(bpe_gpu_ctx *c, const uint32_t *ids, size_t len, const uint64_t *id_off, size_t ndocs,
+                        const uint32_t *pairs, size_t n_merges, uint8_t *out, size_t cap, size_t *out_len,
+                        uint64_t *byte_off) {
+    return decode_docs_run(c, ids, len, id_off, ndocs, pairs, n_merges, nullptr, out, cap, out_len, byte_off);
+}
+
+int bpe_gpu_decode_docs_special(bpe_gpu_ctx *c, const uint32_t *ids, size_t len, const uint64_t *id_off, size_t ndocs,
+                                const uint32_t *pairs, size_t n_merges, const bpe_gpu_specials *specials, uint8_t *out,
+                                size_t cap, size_t *out_len, uint64_t *byte_off) {
+    if (!c) return BPE_GPU_EINVAL;
+    char msg[400];
+    if (bpe_specials_check(specials, msg, sizeof msg)) return fail(BPE_GPU_EINVAL, msg);
+    if (!id_off) {  // one flat sequence
+        if (ndocs) return fail(BPE_GPU_EINVAL, "decode_docs_special: documents without offsets");
+        return decode_run(c, ids, len, pairs, n_merges, specials, out, cap, out_len);
+    }
+    return decode_docs_run(c, ids, len, id_off, ndocs, pairs, n_merges, specials, out, cap, out_len, byte_off);
 }
 
 }  // extern "C"
