@@ -59,7 +59,7 @@ typedef struct {
     uint64_t edge_events;     /* D == resize threshold resolved by emulation   */
     uint64_t rule_ties;       /* schedule-dependent ties decided by the rule (approximate in hot-set mode) */
     uint64_t table_grows;     /* pair-count table regrowths                    */
-    uint64_t keys;            /* slots in use in the pair-count table          */
+    uint64_t keys;            /* slots in use in the pair-count table (informational; dense table: keys created) */
     double ms_init;           /* device-side setup (counting sort, table)      */
     double ms_train;          /* merge loop                                    */
     double ms_total;          /* init + loop (what bench.py times end to end)  */
@@ -115,6 +115,10 @@ typedef struct {
                                  3 the engine's own cap on an unbounded run (2^24 merges; 2^22 over
                                  several devices in compress_multi) before that rule: reported on
                                  stderr too, since the reference has no cap */
+    uint64_t table_dense;     /* training: 1 when the pair table was the dense one (a count per pair of ids,
+                                 chosen when the run has a merge cap and the square of 256 + cap ids is no
+                                 larger than the hash table; BPE_TAB_DENSE=0 / 1 forces either), else 0.
+                                 `keys` then counts the keys created (counts that left 0), not slots taken */
 } bpe_gpu_stats;
 
 /* Per-merge record (training): the structured per-iteration metrics the

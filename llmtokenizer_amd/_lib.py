@@ -72,7 +72,7 @@ class GpuStats(ctypes.Structure):
                                          "end_table", "end_staging")] + \
         [("ms_select_span", ctypes.c_double), ("select_launches", ctypes.c_uint64)] + \
         [(n, ctypes.c_uint64) for n in ("tie_verified", "tie_failed", "keys_zeroed", "keys_skipped", "skip_failed",
-                                         "stop_reason")]
+                                         "stop_reason", "table_dense")]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}

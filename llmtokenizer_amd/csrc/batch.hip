@@ -182,8 +182,8 @@ __device__ __attribute__((always_inline)) inline void bat_block_top(const Eng *_
         KV x = kv_empty();
         if (i < n) {
             const uint32_t slot = base == base0 ? slot0 : E->hot_slot[i];
-            const uint32_t c = E->hcnt[(uint64_t)(slot) * E->hcs];
-            const unsigned long long key = E->hkey[(uint64_t)(slot) * E->hks] - 1;
+            const uint32_t c = *tab_cnt(E, slot);
+            const unsigned long long key = tab_key(E, slot);
             if (c) x = KV{pack_val(c, (uint32_t)(key >> 32), (uint32_t)key, Bsz), key};
         }
         if (E->dbgts && base == base0 && lane == 0) {  // (timeline: this wave's first keys loaded)
@@ -548,7 +548,7 @@ __device__ __attribute__((always_inline)) inline void bselect_block(const Eng *_
         else if ((cnt0 < hotT && hotT > 2) || C->hot_n > HOT_LIMIT) stop = STOP_HOT;
         else if (relist_due) stop = STOP_RELIST;
         else if (v0 == 0 || cnt0 <= 1) stop = STOP_DONE;
-        else if (C->nkeys + 4ull * (256ull + md + 2) >= E->hcap / 2) stop = STOP_GROW;
+        else if (!E->dense && C->nkeys + 4ull * (256ull + md + 2) >= E->hcap / 2) stop = STOP_GROW;
         jst = uni(jst);
         kpr = uni(kpr);
         retry = uni(retry);
@@ -700,7 +700,7 @@ __device__ __attribute__((always_inline)) inline void bselect_block(const Eng *_
                 else if (md + mi >= E->mcap || c <= 1 || (hotT > 2 && c < hotT)) why = 1;
                 else if (tie_rel && !cons_ok && !(opt_ok && E->tie_verify))
                     why = 4;  // (a tie whose order the batch could change, or one running past the list)
-                else if (C->nkeys + 4ull * (256ull + md + mi + 2) * (mi + 1) >= E->hcap / 2) why = 6;
+                else if (!E->dense && C->nkeys + 4ull * (256ull + md + mi + 2) * (mi + 1) >= E->hcap / 2) why = 6;
             }
             // the earlier entries of this list that do not commute with me
             // (one uses my left id on its right or my right id on its left),
@@ -2300,6 +2300,7 @@ __global__ __launch_bounds__(256) void k_bpack(const Eng *__restrict__ E, const 
 
 // ---------------------------------------------------------------- k_bapply
 __device__ inline uint64_t hinsert_c(const Eng *E, uint32_t u, uint32_t v, uint32_t *nins) {
+    if (E->dense) return tab_dslot(E, u, v);
     const unsigned long long key = (((unsigned long long)u << 32) | v) + 1ull;
     const uint64_t msk = E->hcap - 1;
     uint64_t s = mix64(key) & msk;
@@ -2689,6 +2690,7 @@ __global__ __launch_bounds__(1024) void k_bapply(const Eng *__restrict__ E, Ctl 
     // next (the entries, then every update's first-slot probe, then the count
     // atomics): three dependent round trips per round instead of per entry
     const uint64_t hmsk = E->hcap - 1;
+    const bool dense = E->dense != 0;  // (block-uniform)
     const uint32_t step = nB * blockDim.x;
     for (uint32_t t0 = bidB * blockDim.x; t0 < total; t0 += step * AU) {  // uniform per block
         uint32_t m[AU], cat[AU], x[AU], val[AU];
@@ -2717,6 +2719,12 @@ __global__ __launch_bounds__(1024) void k_bapply(const Eng *__restrict__ E, Ctl 
                 else if (cat[q] == V_IL) { u = x[q]; v = z; }
                 else { u = z; v = x[q]; }
                 key[q] = (((unsigned long long)u << 32) | v) + 1ull;
+                if (dense) {
+                    // the slot is the key: no probe, no CAS.  Consecutive lanes hold
+                    // consecutive x, so a DR / IR vector's atomics share their lines
+                    slot[q] = tab_dslot(E, u, v);
+                    continue;
+                }
                 slot[q] = mix64(key[q]) & hmsk;
                 unsigned long long *hk = &E->hkey[slot[q] * E->hks];
                 prev[q] = dneg[q] ? *hk : atomicCAS(hk, 0ull, key[q]);
@@ -2724,7 +2732,7 @@ __global__ __launch_bounds__(1024) void k_bapply(const Eng *__restrict__ E, Ctl 
         }
 #pragma unroll
         for (uint32_t q = 0; q < AU; q++) {
-            if (!act[q]) continue;
+            if (!act[q] || dense) continue;
             if (prev[q] == key[q]) continue;               // found at the first slot
             if (!dneg[q] && prev[q] == 0) { nins++; continue; }  // inserted there
             // (rare: the key sits further along its probe run)
@@ -2746,7 +2754,10 @@ __global__ __launch_bounds__(1024) void k_bapply(const Eng *__restrict__ E, Ctl 
         for (uint32_t q = 0; q < AU; q++) {
             old[q] = 0;
             if (act[q] && slot[q] != ~0ull)
-                old[q] = atomicAdd(&E->hcnt[slot[q] * E->hcs], dneg[q] ? 0u - val[q] : val[q]);
+                old[q] = atomicAdd(tab_cnt(E, slot[q]), dneg[q] ? 0u - val[q] : val[q]);
+            // dense: a decrement of more than the count is the pair that is not there
+            // (the count has wrapped: the run ends on the error below)
+            if (dense && act[q] && dneg[q] && old[q] < val[q]) slot[q] = ~0ull;
         }
         if (E->dbgts && t0 == bidB * blockDim.x) {  // (timeline: the first round's count updates returned)
             __builtin_amdgcn_s_waitcnt(0);
@@ -2767,6 +2778,7 @@ __global__ __launch_bounds__(1024) void k_bapply(const Eng *__restrict__ E, Ctl 
                     dD += (long long)(nw != 0) - (long long)(old[q] != 0);
                     if (!dneg[q] && old[q] == 0 && nw != 0) {  // a key created (new keys only rise)
                         ncre++;
+                        if (dense) nins++;  // (hash: counted when the key took its slot)
                         if (tie) atomicAdd(&s_cnew[m[q]], 1u);
                     }
                     if (dneg[q] && nw == 0 && old[q] != 0) nzero++;
@@ -2878,7 +2890,7 @@ __global__ __launch_bounds__(1024) void k_bapply(const Eng *__restrict__ E, Ctl 
                     const uint32_t slot = E->tlog[3 * (uint64_t)q], d = E->tlog[3 * (uint64_t)q + 1],
                                    mq = E->tlog[3 * (uint64_t)q + 2];
                     if (mq < from) continue;
-                    const uint32_t old = atomicAdd(&E->hcnt[(uint64_t)slot * E->hcs], 0u - d);
+                    const uint32_t old = atomicAdd(tab_cnt(E, slot), 0u - d);
                     rd += (long long)(old - d != 0) - (long long)(old != 0);
                 }
                 dD += rd;  // (this block's sum below carries the whole revert's D change)

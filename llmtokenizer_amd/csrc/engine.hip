@@ -192,8 +192,8 @@ __device__ inline int64_t stat_find(const Eng *E, uint64_t cap, uint32_t t, uint
 // keys of the pair table with count == M
 __global__ void k_res_collect(const Eng *E, uint32_t M, uint32_t *out, uint32_t *n, uint32_t cap) {
     for (uint64_t s = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; s < E->hcap; s += (uint64_t)gridDim.x * blockDim.x) {
-        if (E->hcnt[(uint64_t)(s) * E->hcs] != M) continue;
-        const unsigned long long k = E->hkey[(uint64_t)(s) * E->hks] - 1;
+        if (*tab_cnt(E, s) != M) continue;
+        const unsigned long long k = tab_key(E, s);
         const uint32_t p = atomicAdd(n, 1u);
         if (p < cap) {
             out[2 * p] = (uint32_t)(k >> 32);
@@ -331,6 +331,7 @@ struct bpe_gpu_ctx {
     uint32_t *d_enc_pairs = nullptr;
     hipGraphExec_t g_plain = nullptr, g_tracked = nullptr, g_encode = nullptr, g_batch = nullptr;
     bool hot_fallback = false;  // the hot set was given up for the level summaries
+    bool cap_known = false;     // the caller gave the run a merge cap (setup_run: the dense pair table needs one)
     uint32_t relists = 0;       // byte-pair list rebuilds of the current run
     std::vector<uint64_t> events;  // run events of the current run (bpe_gpu_fetch_events)
     std::vector<hipGraphExec_t> retired;  // replaced graphs, destroyed with the run
@@ -785,12 +786,34 @@ int setup_run_body(bpe_gpu_ctx *c, uint32_t mcap, bool encode) {
     } else {
         h.hcap = 1ull << 16;
     }
+    // the dense layout: one count per pair of ids, count[u * P + v] (no keys, no probe, never regrown), when
+    // the run has a merge cap of the caller's, slots stay 32-bit (hot_slot, the undo log; ~0u stays "none")
+    // and the square is no larger than the hash table would be: 285 MB instead of 3 GiB on configs[2].
+    // BPE_TABLE_SLOTS / BPE_TAB_IL ask for the hash layouts; BPE_TAB_DENSE=0 / 1 forces either
+    h.dense = h.dP = h.dRcp = h.dpad = 0;
+    if (!encode && c->cap_known) {
+        const uint64_t V = h.vcap, P = (V + 31) & ~31ull;
+        const int want_dense = getenv_int("BPE_TAB_DENSE", -1);
+        const bool fits = P * V < (1ull << 32);
+        const bool smaller = 4 * P * V <= 12 * h.hcap && !getenv("BPE_TABLE_SLOTS") && !getenv_int("BPE_TAB_IL", 0);
+        if (fits && want_dense != 0 && (want_dense > 0 || smaller)) {
+            h.dense = 1;
+            h.dP = (uint32_t)P;
+            h.dRcp = (uint32_t)((1ull << 32) / P);
+            h.hcap = (P * V + L1W - 1) / L1W * L1W;
+        }
+    }
+    c->stats.table_dense = h.dense;
     const uint64_t nL1 = h.hcap / L1W, nL2 = (nL1 + L2W - 1) / L2W;
     // the pair table: two arrays (keys, counts); BPE_TAB_IL=1: 16-byte slots
     // {key, count} so that a probe and its count update touch one line -- the
     // same loop time on configs[2] (69.4-70.4 vs 69.5-70.0 ms) and +1.2 ms of
     // init (a 4 GB table to clear and histogram instead of 3 GB), so off
-    if (getenv_int("BPE_TAB_IL", 0)) {
+    if (h.dense) {
+        h.hkey = nullptr;
+        if ((r = dalloc(c, &h.hcnt, h.hcap))) return r;
+        h.hks = h.hcs = 1;
+    } else if (getenv_int("BPE_TAB_IL", 0)) {
         if ((r = dalloc(c, &h.hkey, 2 * h.hcap))) return r;
         h.hcnt = reinterpret_cast<uint32_t *>(h.hkey) + 2;
         h.hks = 2;
@@ -837,6 +860,7 @@ int setup_run_body(bpe_gpu_ctx *c, uint32_t mcap, bool encode) {
 // replace the pair table by one of capacity ncap (keys with count 0 dropped)
 int grow_table(bpe_gpu_ctx *c, uint64_t ncap) {
     Eng &h = c->h;
+    if (h.dense) return fail(BPE_GPU_EINTERNAL, "the dense pair table never regrows");
     unsigned long long *okey = h.hkey;
     uint32_t *ocnt = h.hcnt;
     const uint64_t ocap = h.hcap;
@@ -2626,6 +2650,7 @@ int bpe_gpu_train_ex(bpe_gpu_ctx *c, long max_merges, unsigned flags, size_t *n_
     uint64_t cap = c->n0 - 1;  // a run can never learn more merges than pairs
     cap = std::min<uint64_t>(cap, engine_merge_cap());
     if (max_merges >= 0) cap = std::min<uint64_t>(cap, (uint64_t)max_merges);
+    c->cap_known = max_merges >= 0;
     const double t0 = now_ms();
     int r;
     static const bool dbg_init = getenv_int("BPE_DEBUG_INIT", 0) != 0;

@@ -266,6 +266,11 @@ struct Eng {
     // strides: 1 / 1 two arrays (default); 2 / 4 one array of 16-byte slots
     // {key, count, -} (BPE_TAB_IL=1): a probe and its count update touch one line
     uint32_t hks, hcs;
+    // dense layout (setup_run: when the square of the ids fits): no key array (hkey null), the count of
+    // (u, v) at hcnt[u * dP + v] with dP = vcap rounded up to 32, a count of 0 = an absent key; hcap is
+    // then dP * vcap rounded up to L1W (no power of two), dRcp = floor(2^32 / dP) for the key of a slot
+    // (kernels.hip tab_*)
+    uint32_t dense, dP, dRcp, dpad;
     // max summaries: level 1 = 256 slots, level 2 = 256 level-1 entries;
     // best packed value, number of keys holding it, smallest such key
     unsigned long long *l1best, *l1key;

@@ -529,7 +529,38 @@ __global__ __launch_bounds__(SCAN_T) void k_scan(const Eng *__restrict__ E, Ctl 
 }
 
 // --------------------------------------------------------------- pair table
+// Two layouts (Eng::dense, the same for a whole run): the hash table below, or
+// one count per pair of ids at hcnt[u * dP + v] with no key array.  Every
+// access goes through these (slot -> count pointer, slot -> key, dense slot of
+// a key) and the find / insert functions below.
+__device__ inline uint32_t *tab_cnt(const Eng *E, uint64_t slot) { return &E->hcnt[slot * E->hcs]; }
+// dense: the slot of (u, v); ~0 for an id outside the vocabulary (callers flag the error, as for a full table)
+__device__ inline uint64_t tab_dslot(const Eng *E, uint32_t u, uint32_t v) {
+    return u < E->vcap && v < E->vcap ? (uint64_t)u * E->dP + v : ~0ull;
+}
+// key (u << 32 | v) of a slot that holds one
+__device__ inline unsigned long long tab_key(const Eng *E, uint64_t slot) {
+    if (E->dense) {
+        // slot / dP: the reciprocal's quotient is the true one or one less
+        const uint32_t s = (uint32_t)slot, P = E->dP;
+        uint32_t q = __umulhi(s, E->dRcp), r = s - q * P;
+        if (r >= P) {
+            q++;
+            r -= P;
+        }
+        return ((unsigned long long)q << 32) | r;
+    }
+    return E->hkey[slot * E->hks] - 1;
+}
+// (a table scan's test for a live key is the count in both layouts: dense, a
+// count of 0 is an absent key; hash, a key whose count fell to 0 stays in its
+// slot and is passed over)
+
 __device__ inline uint64_t hfind(const Eng *E, uint32_t u, uint32_t v) {
+    if (E->dense) {
+        const uint64_t s = tab_dslot(E, u, v);
+        return s != ~0ull && *tab_cnt(E, s) ? s : ~0ull;
+    }
     const unsigned long long key = (((unsigned long long)u << 32) | v) + 1ull;
     const uint64_t m = E->hcap - 1;
     uint64_t s = mix64(key) & m;
@@ -545,6 +576,7 @@ __device__ inline uint64_t hfind(const Eng *E, uint32_t u, uint32_t v) {
 // nins != null: count a new key there instead of in C->nkeys (the caller
 // adds its block's total once: ~200 same-address atomics per merge otherwise)
 __device__ inline uint64_t hinsert(const Eng *E, Ctl *C, uint32_t u, uint32_t v, uint32_t *nins = nullptr) {
+    if (E->dense) return tab_dslot(E, u, v);  // (the caller counts the key when it gives it a count)
     const unsigned long long key = (((unsigned long long)u << 32) | v) + 1ull;
     const uint64_t m = E->hcap - 1;
     uint64_t s = mix64(key) & m;
@@ -569,6 +601,14 @@ __device__ inline uint64_t hinsert(const Eng *E, Ctl *C, uint32_t u, uint32_t v,
 // in one round trip (*hit: found there, *cnt / *bv2 valid)
 __device__ inline uint64_t hfind_b(const Eng *E, uint32_t u, uint32_t v, bool *hit, uint32_t *cnt,
                                    unsigned long long *bv2) {
+    if (E->dense) {  // (the caller checks the count against its decrement)
+        const uint64_t s = tab_dslot(E, u, v);
+        if (s == ~0ull) return s;
+        *hit = true;
+        *cnt = *tab_cnt(E, s);
+        *bv2 = E->l1v2[s / L1W];
+        return s;
+    }
     const unsigned long long key = (((unsigned long long)u << 32) | v) + 1ull;
     const uint64_t m = E->hcap - 1;
     const uint64_t s0 = mix64(key) & m;
@@ -597,6 +637,7 @@ __device__ inline uint64_t hfind_b(const Eng *E, uint32_t u, uint32_t v, bool *h
 // inserted keys counted in *nins
 __device__ inline uint64_t hinsert_b(const Eng *E, uint32_t u, uint32_t v, uint32_t *nins, bool *fresh,
                                      unsigned long long *bv2) {
+    if (E->dense) return tab_dslot(E, u, v);  // (no slot to take: the caller loads the count, 0 for a new key)
     const unsigned long long key = (((unsigned long long)u << 32) | v) + 1ull;
     const uint64_t m = E->hcap - 1;
     uint64_t s = mix64(key) & m;
@@ -820,15 +861,17 @@ __device__ inline void apply_body(const Eng *__restrict__ E, Ctl *__restrict__ C
                 unsigned long long fbv2 = 0;
                 const uint64_t slot = d > 0 ? hinsert_b(E, u, v, &nins, &fresh, &fbv2) : hfind_b(E, u, v, &fresh, &fold, &fbv2);
                 if (!UNDO && E->dbgts) (d > 0 ? tprobe : tcount) = wall_clock64();  // (debug: insert / find)
-                if (slot == ~0ull) {
+                const uint32_t old = slot == ~0ull ? 0u : fresh ? fold : *tab_cnt(E, slot);
+                // (dense: no key to miss -- a decrement of more than the count is the absent pair)
+                if (slot == ~0ull || (E->dense && d < 0 && (long long)old + d < 0)) {
                     C->err = d > 0 ? 2 : 1;  // k_select stops on it
                 } else {
                     blk = (uint32_t)(slot / L1W);
-                    const uint32_t old = fresh ? fold : E->hcnt[(uint64_t)(slot) * E->hcs];
                     const unsigned long long bv2 = fresh ? fbv2 : E->l1v2[blk];  // loaded beside the count
 
                     const uint32_t nw = (uint32_t)((long long)old + d);
-                    E->hcnt[(uint64_t)(slot) * E->hcs] = nw;
+                    *tab_cnt(E, slot) = nw;
+                    if (E->dense && !UNDO && old == 0 && nw != 0) nins++;  // a key created
                     dD += (long long)(nw != 0) - (long long)(old != 0);
                     if (hot) {
                         // a rise to >= hot_T lists the key (once: counts only rise
@@ -1045,13 +1088,13 @@ __device__ __forceinline__ void rescan1_body(const Eng *__restrict__ E, Ctl *__r
 #pragma unroll
             for (uint32_t q = 0; q < HQ; q++) {
                 const uint64_t slot = (uint64_t)blk * L1W + (h * HQ + q) * 64 + lane;
-                cnt[q] = E->hcnt[(uint64_t)(slot) * E->hcs];
-                key[q] = E->hkey[(uint64_t)(slot) * E->hks];
+                cnt[q] = *tab_cnt(E, slot);
+                key[q] = tab_key(E, slot);
             }
 #pragma unroll
             for (uint32_t q = 0; q < HQ; q++) {
                 if (cnt[q]) {
-                    const unsigned long long k = key[q] - 1;
+                    const unsigned long long k = key[q];
                     mine = top2_merge(mine, top2_one(pack_val(cnt[q], (uint32_t)(k >> 32), (uint32_t)k, B), 1, k));
                 }
             }
@@ -1083,8 +1126,8 @@ __device__ void hot_reduce_body(const Eng *__restrict__ E, Ctl *__restrict__ C, 
     const uint32_t i0 = bid * blockDim.x + threadIdx.x;
     for (uint32_t i = i0; i < n; i += nblk * blockDim.x) {
         const uint32_t slot = i == i0 && slot0 != HOLE ? slot0 : E->hot_slot[i];
-        const uint32_t c = E->hcnt[(uint64_t)(slot) * E->hcs];
-        const unsigned long long k = E->hkey[(uint64_t)(slot) * E->hks] - 1;
+        const uint32_t c = *tab_cnt(E, slot);
+        const unsigned long long k = tab_key(E, slot);
         if (c) mine = top2_merge(mine, top2_one(pack_val(c, (uint32_t)(k >> 32), (uint32_t)k, B), 1, k));
     }
     mine = wave_top2(mine);
@@ -1121,7 +1164,7 @@ __global__ __launch_bounds__(256) void k_hot_hist(const Eng *__restrict__ E, con
     if (slots) {
         for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < ns; i += gridDim.x * blockDim.x) {
             const uint32_t s = slots[i];
-            const uint32_t c = s != ~0u ? E->hcnt[(uint64_t)(s) * E->hcs] : 0u;
+            const uint32_t c = s != ~0u ? *tab_cnt(E, s) : 0u;
             if (c >= 2) atomicAdd(&h[hot_bin(c)], 1u);
         }
     } else if (E->hcs == 4) {  // 16-byte slots {key, count, -}: one uint4 per slot
@@ -1224,7 +1267,7 @@ __global__ __launch_bounds__(256) void k_hot_collect(const Eng *__restrict__ E, 
     const uint64_t end = (n + stride - 1) / stride * stride;  // uniform trip count (wave_append)
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < end; i += stride) {
         const uint32_t s = i < n ? (slots ? slots[i] : (uint32_t)i) : ~0u;
-        const bool in = s != ~0u && E->hcnt[(uint64_t)(s) * E->hcs] >= T;
+        const bool in = s != ~0u && *tab_cnt(E, s) >= T;
         const uint32_t p = wave_append(in, &C->hot_n);
         if (in && p < HOT_CAP) E->hot_slot[p] = s;
     }
@@ -1529,7 +1572,7 @@ __device__ inline void select_tail(const Eng *__restrict__ E, Ctl *C, Ctl *Cg, T
         if (cs > os && cs - os >= E->relist_stale) { C->stop = STOP_RELIST; return; }
     }
     if (r.v == 0 || cnt <= 1) { C->stop = STOP_DONE; return; }
-    if (C->nkeys + 4ull * (256ull + C->merges_done + 2) >= E->hcap / 2) { C->stop = STOP_GROW; return; }
+    if (!E->dense && C->nkeys + 4ull * (256ull + C->merges_done + 2) >= E->hcap / 2) { C->stop = STOP_GROW; return; }
     const bool tracked = !E->fast && C->n_live < DYN_LIMIT;  // deterministic (static) reference iteration
     if (tracked && (edge || r.tie > 1)) { C->stop = STOP_EVENT; return; }
     // untracked tie (n >= 2^20, schedule-dependent in the reference): the
@@ -3121,7 +3164,8 @@ __global__ void k_init_counts(const Eng *__restrict__ E, Ctl *__restrict__ C, co
     const uint32_t u = unrank[k / E->A], v = unrank[k % E->A];
     const uint64_t slot = hinsert(E, C, u, v);
     if (slot == ~0ull) { C->err = 2; C->stop = STOP_ERROR; return; }
-    E->hcnt[(uint64_t)(slot) * E->hcs] = c;
+    *tab_cnt(E, slot) = c;
+    if (E->dense) atomicAdd(&C->nkeys, 1ull);  // (hash: hinsert counted it)
     if (slots) slots[k] = (uint32_t)slot;
     atomicAdd(&C->D, 1ull);
 }
@@ -3136,7 +3180,7 @@ __global__ void k_rehash(const Eng *__restrict__ E, Ctl *__restrict__ C, const u
         if (!oc) continue;  // zero-count keys are dropped on regrowth
         const uint64_t slot = hinsert(E, C, (uint32_t)((k - 1) >> 32), (uint32_t)(k - 1));
         if (slot == ~0ull) { C->err = 2; C->stop = STOP_ERROR; return; }
-        E->hcnt[(uint64_t)(slot) * E->hcs] = oc;
+        *tab_cnt(E, slot) = oc;
     }
 }
 

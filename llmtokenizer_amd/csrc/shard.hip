@@ -593,6 +593,7 @@ int group_train(bpe_gpu_group *g, long max_merges, size_t *n_merges) {
         c->shard = g->shard0 + k;
         c->nshards = g->nshards;
         c->ntot = ntot;
+        c->cap_known = max_merges >= 0;
         // batches: schedule-free ties (sharded runs always), dense exchange
         // vectors over the whole vocabulary, a mailbox slot that holds them
         const uint64_t vc = 256 + cap;
@@ -743,6 +744,7 @@ int group_train(bpe_gpu_group *g, long max_merges, size_t *n_merges) {
     g->stats.rule_ties = C.counters[2];
     g->stats.keys = C.nkeys;
     g->stats.table_grows = g->cs[0]->stats.table_grows;
+    g->stats.table_dense = g->cs[0]->stats.table_dense;
     g->stats.l1_rescanned = C.counters[6];
     if (getenv("BPE_DEBUG") && C.counters[7])
         fprintf(stderr, "fused sharded K1 (us/merge): records pulled after %.2f; select phases (us): "

@@ -12,11 +12,12 @@
 // lines_per_s counts the distinct 128-B lines each gather touches.
 //
 // build: hipcc --offload-arch=gfx950 -O3 -o tools/gather_bench tools/gather_bench.hip
-// run:   tools/gather_bench [buf_mib=4096] [n_idx_m=64]
+// run:   tools/gather_bench [buf_mib=4096] [n_idx_m=64] [atomics: the returning-atomic modes alone, random and row]
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 
 #define CHK(x)                                                                     \
     do {                                                                           \
@@ -27,9 +28,9 @@
         }                                                                          \
     } while (0)
 
-enum { M_A4 = 0, M_V16 = 1, M_W32 = 2, M_ATOM = 3, M_ATOMRET = 4, M_STREAM = 5, M_ST4 = 6, M_ST8 = 7 };
+enum { M_A4 = 0, M_V16 = 1, M_W32 = 2, M_ATOM = 3, M_ATOMRET = 4, M_STREAM = 5, M_ST4 = 6, M_ST8 = 7, M_ATOMROW = 8 };
 static const char *mode_name[] = {"load4", "load16", "window32", "atomic_noret", "atomic_ret", "stream16", "store4",
-                                  "store_pair"};
+                                  "store_pair", "atomic_ret_row"};
 
 __device__ inline uint64_t mix64(uint64_t x) {
     x ^= x >> 33;
@@ -64,6 +65,18 @@ __global__ __launch_bounds__(256) void k_gather(const uint32_t *__restrict__ idx
         for (int u = 0; u < U; u++) {
             const uint64_t e = e0 + u * stride;
             p[u] = e < n_idx ? idx[e] : 0u;
+        }
+        if (MODE == M_ATOMROW) {
+            // the dense pair table's row half: a wave's 64 lanes cover 64 consecutive dwords of a row at a
+            // random 256-B aligned base, 1 lane in 5 holding an update (returning u32 atomic); n_idx / 5 atomics
+#pragma unroll
+            for (int u = 0; u < U; u++) {
+                const uint64_t e = e0 + u * stride;
+                const uint32_t base = p[u] & ~63u;  // (the lanes of a wave must agree: lane 0's index)
+                const uint32_t row = __shfl(base, 0, 64) + (uint32_t)(e & 63);
+                if (e < n_idx && mix64(e * 7 + 1) % 5 == 0) acc += atomicAdd(&buf[row], 1u);
+            }
+            continue;
         }
         if (MODE == M_ATOM) {
 #pragma unroll
@@ -126,6 +139,7 @@ static double lines_per_gather(int mode) {
     switch (mode) {
     case M_W32: return 1.0 + 16.0 / 128.0;  // 32 B at a 16-B aligned base: crosses a line when base % 128 == 112
     case M_ST8: return 1.0 + 4.0 / 128.0;  // 8 B at a 4-B aligned base: crosses a line when base % 128 == 124
+    case M_ATOMROW: return 2.0 * 5.0 / 64.0;  // 64 lanes x 4 B = two lines per 64 / 5 atomics
     default: return 1.0;
     }
 }
@@ -142,7 +156,7 @@ static void sweep(const uint32_t *idx, uint64_t n_idx, uint32_t *buf, uint32_t *
         ms[3] = run<MODE, 8>(idx, n_idx, buf, out, grid, 5);
         const int us[] = {1, 2, 4, 8};
         for (int k = 0; k < 4; k++) {
-            const double gps = (double)n_idx / (ms[k] * 1e-3);
+            const double gps = (double)n_idx / (MODE == M_ATOMROW ? 5 : 1) / (ms[k] * 1e-3);
             printf("{\"mode\": \"%s\", \"U\": %d, \"waves_per_cu\": %d, \"buf_mib\": %llu, \"n\": %llu, \"ms\": %.4f, "
                    "\"gathers_per_s\": %.4e, \"lines_per_s\": %.4e}\n",
                    mode_name[MODE], us[k], waves[wi], (unsigned long long)buf_mib, (unsigned long long)n_idx, ms[k], gps,
@@ -165,6 +179,13 @@ int main(int argc, char **argv) {
     k_fill_buf<<<2048, 256>>>(buf, nbuf);
     k_fill_idx<<<2048, 256>>>(idx, n_idx, nbuf - 8, 12345);
     CHK(hipDeviceSynchronize());
+    if (argc > 3 && !strcmp(argv[3], "atomics")) {
+        // returning u32 atomics alone: random over the buffer, and the row shape (say buf_mib = 272 for
+        // the dense pair table of configs[2])
+        sweep<M_ATOMRET>(idx, n_idx, buf, out, buf_mib, ncu);
+        sweep<M_ATOMROW>(idx, n_idx, buf, out, buf_mib, ncu);
+        return 0;
+    }
     sweep<M_A4>(idx, n_idx, buf, out, buf_mib, ncu);
     sweep<M_V16>(idx, n_idx, buf, out, buf_mib, ncu);
     sweep<M_W32>(idx, n_idx, buf, out, buf_mib, ncu);
