@@ -40,7 +40,7 @@ $(BUILD):
 $(BUILD)/engine.o: $(HIPDEPS) | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $(PKG)/csrc/engine.hip -o $@
 
-$(BUILD)/%.o: $(PKG)/src/%.c $(wildcard include/*.h $(PKG)/src/*.h) | $(BUILD)
+$(BUILD)/%.o: $(PKG)/src/%.c $(wildcard include/*.h $(PKG)/src/*.h $(PKG)/csrc/unicode_classes.h) | $(BUILD)
 	$(CC) $(CFLAGS) -c $< -o $@
 
 $(PKG)/libbpe_amd.so: $(BUILD)/engine.o $(COBJ) $(COBJ_GPU) $(COBJ_TS) $(COBJ_SP) $(COBJ_SPECIAL)
@@ -108,3 +108,13 @@ tests/asan_special/asan_special: tests/asan_special/asan_special.c $(CSRC_SPECIA
 
 asan-special: tests/asan_special/asan_special
 .PHONY: asan-special
+
+# BPE_SPLIT_GPT2_UNICODE's host code (the class table, the rule in src/bpe_split_preset.c and the preset through
+# src/bpe_special.c) the same way, in a stand-alone program that calls no engine function
+# (tests/asan_split_unicode/asan_split_unicode.c); run by tests/test_asan_split_unicode.py
+tests/asan_split_unicode/asan_split_unicode: tests/asan_split_unicode/asan_split_unicode.c $(CSRC_SPECIAL) $(CSRC_SP) $(wildcard include/*.h $(PKG)/src/*.h $(PKG)/csrc/unicode_classes.h)
+	$(CC) -O1 -g -std=c11 -D_GNU_SOURCE -fno-omit-frame-pointer -fsanitize=address,undefined \
+	    -fno-sanitize-recover=undefined -Iinclude -o $@ tests/asan_split_unicode/asan_split_unicode.c $(CSRC_SPECIAL) $(CSRC_SP) -lm
+
+asan-split-unicode: tests/asan_split_unicode/asan_split_unicode
+.PHONY: asan-split-unicode

@@ -74,12 +74,19 @@ uint32_t *bpe_encode_split(const uint8_t *bytes, size_t n, const uint8_t *cls, c
 dyn_arr_t *bpe_train_split(const uint8_t *bytes, size_t n, const uint8_t *cls, const uint16_t *brk, long max_merges,
                            int device);
 
-/* The preset split rules (bpe_gpu.h: BPE_SPLIT_LINES, BPE_SPLIT_WORDS, BPE_SPLIT_GPT2) in plain C, on
+/* The preset split rules (bpe_gpu.h: BPE_SPLIT_LINES, BPE_SPLIT_WORDS, BPE_SPLIT_GPT2, BPE_SPLIT_GPT2_UNICODE) in plain C, on
  * the host and without a GPU: the written definition bpe_gpu_split_preset is held to, and the
  * yardstick for inputs too large for a regular-expression engine.  Two-phase like the fetch calls:
  * out may be NULL, *count = pieces + 1 (the piece starts followed by n; n == 0: the single offset 0),
  * and at most cap entries are written.  BPE_GPU_EINVAL for another preset or a bad argument. */
 int bpe_split_offsets_host(int preset, const uint8_t *bytes, size_t n, uint64_t *out, size_t cap, size_t *count);
+
+/* The classes of BPE_SPLIT_GPT2_UNICODE (bpe_gpu.h), pure host functions.  bpe_unicode_class: the class of a
+ * code point, 0 P, 1 L (\p{L}), 2 N (\p{N}), 3 S (U+0020), 4 W (the other White_Space); P above U+10FFFF.
+ * bpe_unicode_info: *source = where the committed table came from ("regex <version>", a static string),
+ * *digest = the FNV-1a 64 of the 0x110000 classes as bytes in code point order; either may be NULL.  Returns 0. */
+int bpe_unicode_class(uint32_t cp);
+int bpe_unicode_info(const char **source, uint64_t *digest);
 
 /* bpe_encode_split with a preset in place of the tables (bpe_gpu_split_preset): the way to
  * BPE_SPLIT_GPT2, which no two tables express.  Results and ownership as bpe_encode_split. */

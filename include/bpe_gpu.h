@@ -293,6 +293,37 @@ int bpe_gpu_docs_window(const uint64_t *doc_off, size_t ndocs, uint64_t n,
  * So a start depends on b[i - 4 .. i + 1] and on n alone.  bpe_ex.h's
  * bpe_split_offsets_host is this rule in plain C.
  *
+ * BPE_SPLIT_GPT2_UNICODE is the pattern with its Unicode classes, over the text
+ * decoded as UTF-8 (no table rule either).  Its pieces are the successive
+ * matches of
+ *   's|'t|'re|'ve|'m|'ll|'d| ?\p{L}+| ?\p{N}+| ?[^\s\p{L}\p{N}]+|\s+(?!\S)|\s+
+ * reported as byte offsets, with \s Unicode White_Space (25 code points:
+ * U+0009-000D, 0020, 0085, 00A0, 1680, 2000-200A, 2028, 2029, 202F, 205F, 3000;
+ * not U+001C-001F) and the text decoded as Python's errors="surrogateescape"
+ * does.  As a function of the bytes:
+ *   Characters.  Byte i leads a character when b[i ..] inside the text begins
+ *     with a well-formed UTF-8 sequence (Unicode Table 3-7: no overlong form, no
+ *     surrogate, nothing above U+10FFFF, no sequence cut by n); the sequence's
+ *     other bytes are its continuation bytes.  Every byte in no well-formed
+ *     sequence is a character of its own with class P.  A lead byte never lies
+ *     inside another sequence, so "well-formed at i" is a function of
+ *     b[i .. i + 3] and n alone.
+ *   Classes.  A character is S if it is U+0020, else W if it is White_Space,
+ *     else L if \p{L}, else N if \p{N}, else P (csrc/unicode_classes.h: the
+ *     classes of every code point, the source they came from and their digest;
+ *     bpe_ex.h bpe_unicode_class / bpe_unicode_info).  K[i] is the class of the
+ *     character byte i belongs to, end(i) the offset just past that character.
+ *   Starts.  Byte 0 starts a piece; a continuation byte never does; any other i
+ *     is decided by the BPE_SPLIT_GPT2 rule above with c = K[i], p = K[i - 1],
+ *     clen(j) unchanged but for its look-back, which reads K[j - 1], and with
+ *     the white-space look-ahead at end(i) in place of i + 1: c ws is a start if
+ *     p is not ws, or if end(i) < n and K[end(i)] is not ws.
+ * So a start depends on b[i - 7 .. i + 7] and n alone, and on a window whose
+ * bytes are all below 0x80 the rule equals BPE_SPLIT_GPT2.  Where this
+ * formulation and the regular expression disagree the expression is the
+ * definition.  cl100k's \p{N}{1,3} and case-insensitive contractions are other
+ * patterns and not offered.
+ *
  * The offsets belong to the loaded bytes.  bpe_gpu_load / _load_fd / _synth /
  * _trim, bpe_gpu_train / _train_ex and a sharded group's load, synth and train
  * on the context drop them; bpe_gpu_encode, _encode_docs, _encode_split and
@@ -300,19 +331,20 @@ int bpe_gpu_docs_window(const uint64_t *doc_off, size_t ndocs, uint64_t n,
  * bpe_gpu_split replaces them.  A call that needs them and finds none returns
  * BPE_GPU_ESTATE.
  * ---------------------------------------------------------------------- */
-enum { BPE_SPLIT_LINES = 0, BPE_SPLIT_WORDS = 1, BPE_SPLIT_GPT2 = 2 };
+enum { BPE_SPLIT_LINES = 0, BPE_SPLIT_WORDS = 1, BPE_SPLIT_GPT2 = 2, BPE_SPLIT_GPT2_UNICODE = 4 }; /* (3 is no preset) */
 /* bytes one workgroup of the split kernels handles per step, and the largest grid
    (a corpus of more than TILE * GRID bytes is walked in grid strides) */
 #define BPE_GPU_SPLIT_TILE 4096
 #define BPE_GPU_SPLIT_GRID 2048
-/* fill cls[256] / brk[16] with a table preset (pure function, no GPU); BPE_SPLIT_GPT2 has no tables: BPE_GPU_EINVAL */
+/* fill cls[256] / brk[16] with a table preset (pure function, no GPU); BPE_SPLIT_GPT2 and BPE_SPLIT_GPT2_UNICODE
+   have no tables: BPE_GPU_EINVAL */
 int bpe_gpu_split_rule(int preset, uint8_t *cls, uint16_t *brk);
 /* out4 = {BPE_GPU_SPLIT_TILE, BPE_GPU_SPLIT_TILE * BPE_GPU_SPLIT_GRID, 0, 0} (pure function, no GPU) */
 int bpe_gpu_split_info(uint64_t *out4);
 /* split the loaded bytes; *ndocs = pieces.  A cls entry above 15 is BPE_GPU_EINVAL. */
 int bpe_gpu_split(bpe_gpu_ctx *ctx, const uint8_t *cls, const uint16_t *brk, size_t *ndocs);
-/* the same by a preset: BPE_SPLIT_LINES / BPE_SPLIT_WORDS are bpe_gpu_split with their tables, BPE_SPLIT_GPT2
-   marks the starts with a kernel of its own; the offsets and all that is said of them above are the same.
+/* the same by a preset: BPE_SPLIT_LINES / BPE_SPLIT_WORDS are bpe_gpu_split with their tables, BPE_SPLIT_GPT2 and
+   BPE_SPLIT_GPT2_UNICODE mark the starts with kernels of their own; the offsets and all that is said of them above are the same.
    BPE_GPU_EINVAL for another preset, BPE_GPU_ESTATE before a load. */
 int bpe_gpu_split_preset(bpe_gpu_ctx *ctx, int preset, size_t *ndocs);
 /* the last split's offsets; out may be NULL, *count = ndocs + 1 */
@@ -386,7 +418,9 @@ int bpe_gpu_fetch_piece_table(bpe_gpu_ctx *ctx, uint64_t *start, uint32_t *len, 
  * differently: looking back from byte i, everything at or before the nearest
  * match byte reads as a newline; looking ahead, a match byte reads as a space, as
  * the bytes at and past n do.  Only positions s - 1 and e .. e + 3 can differ
- * from the marks without specials.  With S == 0 the offsets are those of
+ * from the marks without specials.  BPE_SPLIT_GPT2_UNICODE reads the bytes near
+ * a match the same way, before decoding (a sequence a match cuts is ill-formed);
+ * there positions s - 7 .. s - 1 and e .. e + 6 can differ.  With S == 0 the offsets are those of
  * bpe_gpu_split / bpe_gpu_split_preset.
  *
  * Ids.  Special j (the caller's list order) has the id 256 + n_merges + j for

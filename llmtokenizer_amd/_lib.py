@@ -23,6 +23,7 @@ EXPORTS = [
     "compress_ex", "bpe_train_bytes", "bpe_encode_bytes", "bpe_last_stats",
     "bpe_train_bytes_devices", "compress_multi", "bpe_release_engines", "bpe_encode_docs", "bpe_decode_docs",
     "bpe_encode_split", "bpe_train_split", "bpe_split_offsets_host", "bpe_encode_split_preset", "bpe_train_split_preset",
+    "bpe_unicode_class", "bpe_unicode_info",
     # bpe_gpu.h
     "bpe_gpu_device_count", "bpe_gpu_create", "bpe_gpu_destroy", "bpe_gpu_load", "bpe_gpu_synth",
     "bpe_gpu_train", "bpe_gpu_fetch_merges", "bpe_gpu_fetch_ids", "bpe_gpu_encode", "bpe_gpu_decode",
@@ -222,6 +223,8 @@ def load():
     L.bpe_encode_split_preset.restype = u32p
     L.bpe_train_split_preset.argtypes = [vp, sz, ctypes.c_int, ctypes.c_long, ctypes.c_int]
     L.bpe_train_split_preset.restype = ctypes.POINTER(DynArr)
+    L.bpe_unicode_class.argtypes = [ctypes.c_uint32]
+    L.bpe_unicode_info.argtypes = [ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_uint64)]
     spp = ctypes.POINTER(Specials)
     L.bpe_gpu_split_special.argtypes = [vp, ctypes.c_int, vp, vp, spp, ctypes.POINTER(sz)]
     L.bpe_gpu_split_special_info.argtypes = [vp, vp]

@@ -172,19 +172,42 @@ def encode_batch(docs, merges, device=0):
     return _take_ids(p, n.value), offsets
 
 
-SPLIT_PRESETS = {"lines": 0, "words": 1, "gpt2": 2}  # bpe_gpu.h BPE_SPLIT_LINES / BPE_SPLIT_WORDS / BPE_SPLIT_GPT2
+# bpe_gpu.h BPE_SPLIT_LINES / BPE_SPLIT_WORDS / BPE_SPLIT_GPT2 / BPE_SPLIT_GPT2_UNICODE (3 is no preset)
+SPLIT_PRESETS = {"lines": 0, "words": 1, "gpt2": 2, "gpt2_unicode": 4}
 TABLE_PRESETS = ("lines", "words")  # the presets two tables express
+
+
+def _no_tables(rule):
+    """is rule the name of a preset without tables ("gpt2", "gpt2_unicode": the preset calls run them)?"""
+    return isinstance(rule, str) and rule in SPLIT_PRESETS and rule not in TABLE_PRESETS
+
+
+UNICODE_CLASSES = ("P", "L", "N", "S", "W")
+
+
+def unicode_class(cp):
+    """The class of code point cp under "gpt2_unicode" (bpe_ex.h bpe_unicode_class): "L" \\p{L}, "N" \\p{N},
+    "S" U+0020, "W" the other White_Space, "P" the rest (and everything above U+10FFFF).  No GPU."""
+    return UNICODE_CLASSES[_lib.load().bpe_unicode_class(int(cp))]
+
+
+def unicode_info():
+    """{"source", "digest"}: where the committed class table came from ("regex <version>") and the FNV-1a 64
+    of the 0x110000 classes as bytes 0 P, 1 L, 2 N, 3 S, 4 W (bpe_ex.h bpe_unicode_info).  No GPU."""
+    src, dig = ctypes.c_char_p(), ctypes.c_uint64(0)
+    _lib.check(_lib.load().bpe_unicode_info(ctypes.byref(src), ctypes.byref(dig)), "unicode_info")
+    return {"source": src.value.decode(), "digest": int(dig.value)}
 
 
 def split_rule(preset):
     """The tables (cls uint8[256], brk uint16[16]) of a preset split rule, "lines"
     or "words" (bpe_gpu.h bpe_gpu_split_rule; this project's rules, not GPT-2's
     regular expression): a piece starts at byte i when bit cls[b[i]] of
-    brk[cls[b[i - 1]]] is set, and at byte 0.  "gpt2" has no tables (a start
-    there depends on six bytes): pass the name to split / encode_split /
-    train_split / split_host."""
-    if preset == "gpt2":
-        raise BpeError('split_rule: the rule "gpt2" has no tables: pass its name as the rule')
+    brk[cls[b[i - 1]]] is set, and at byte 0.  "gpt2" and "gpt2_unicode" have no
+    tables (a start there depends on six and fifteen bytes): pass the name to
+    split / encode_split / train_split / split_host."""
+    if _no_tables(preset):
+        raise BpeError(f'split_rule: the rule "{preset}" has no tables: pass its name as the rule')
     if preset not in TABLE_PRESETS:
         raise BpeError(f"split_rule: no preset {preset!r} (have {sorted(SPLIT_PRESETS)})")
     L = _lib.load()
@@ -251,7 +274,7 @@ def split_host_special(data: bytes, rule, specials):
 
 def split_host(data: bytes, rule, specials=None):
     """The offsets (uint64: the piece starts followed by len(data)) of a preset
-    rule, "lines", "words" or "gpt2", computed on the host in plain C
+    rule, "lines", "words", "gpt2" or "gpt2_unicode", computed on the host in plain C
     (bpe_ex.h bpe_split_offsets_host): the definition Engine.split(rule) is held
     to.  With specials (a list of bytes-like objects, see check_specials) the
     definition of Engine.split(rule, specials), for a preset or a (cls, brk)
@@ -290,8 +313,8 @@ def _rule_tables(rule):
 
 
 def encode_split(data: bytes, merges, rule="words", device=0, specials=None):
-    """Split data into pieces on the GPU (rule: a preset name, "lines", "words" or
-    "gpt2", or a (cls, brk) pair, see split_rule) and encode the pieces as documents.  Returns (ids,
+    """Split data into pieces on the GPU (rule: a preset name, "lines", "words",
+    "gpt2" or "gpt2_unicode", or a (cls, brk) pair, see split_rule) and encode the pieces as documents.  Returns (ids,
     id_offsets, byte_offsets), both offsets uint64 of length pieces + 1: piece d
     is data[byte_offsets[d]:byte_offsets[d + 1]] and its ids are
     ids[id_offsets[d]:id_offsets[d + 1]] == encode(piece d, merges).  With specials (a list of
@@ -300,7 +323,7 @@ def encode_split(data: bytes, merges, rule="words", device=0, specials=None):
     L = _lib.load()
     if specials is not None:
         check_specials(specials)
-    gpt2 = isinstance(rule, str) and rule == "gpt2"
+    gpt2 = _no_tables(rule)
     cls, brk = (None, None) if gpt2 or specials is not None else _rule_tables(rule)
     buf = np.frombuffer(data, dtype=np.uint8)
     arr = _merges_to_arr(merges)
@@ -346,7 +369,7 @@ def train_split(data: bytes, rule="words", max_merges=-1, device=0, specials=Non
         preset, pc, pb, keep = _rule_args(rule)
         arr = L.bpe_train_split_special(buf.ctypes.data_as(vp), buf.size, preset, pc, pb, sp.ref, int(max_merges),
                                         int(device))
-    elif isinstance(rule, str) and rule == "gpt2":
+    elif _no_tables(rule):
         arr = L.bpe_train_split_preset(buf.ctypes.data_as(vp), buf.size, SPLIT_PRESETS[rule], int(max_merges),
                                        int(device))
     else:
@@ -492,7 +515,7 @@ class Engine:
 
     def split(self, rule="words", specials=None):
         """split the resident bytes into pieces on the device (rule: a preset
-        name, "lines", "words" or "gpt2", or a (cls, brk) pair, see split_rule); the offsets stay in HBM for
+        name, "lines", "words", "gpt2" or "gpt2_unicode", or a (cls, brk) pair, see split_rule); the offsets stay in HBM for
         encode_split().  With specials (a list of bytes-like objects, see check_specials) every occurrence of
         one is a piece of its own (bpe_gpu_split_special); they last as long as the offsets, and a split
         without them forgets them.  Returns the number of pieces."""
@@ -503,7 +526,7 @@ class Engine:
             preset, pc, pb, keep = _rule_args(rule)
             _lib.check(self.L.bpe_gpu_split_special(self.ctx, preset, pc, pb, sp.ref, ctypes.byref(nd)), "split")
             return nd.value
-        if isinstance(rule, str) and rule == "gpt2":  # no tables: the preset call (bpe_gpu_split_preset)
+        if _no_tables(rule):  # the preset call (bpe_gpu_split_preset)
             _lib.check(self.L.bpe_gpu_split_preset(self.ctx, SPLIT_PRESETS[rule], ctypes.byref(nd)), "split")
             return nd.value
         cls, brk = _rule_tables(rule)

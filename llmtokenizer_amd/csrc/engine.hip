@@ -3474,6 +3474,8 @@ int bpe_gpu_split_rule(int preset, uint8_t *cls, uint16_t *brk) {
         return 0;
     }
     if (preset == BPE_SPLIT_GPT2) return fail(BPE_GPU_EINVAL, "split_rule: BPE_SPLIT_GPT2 has no tables (bpe_gpu_split_preset)");
+    if (preset == BPE_SPLIT_GPT2_UNICODE)
+        return fail(BPE_GPU_EINVAL, "split_rule: BPE_SPLIT_GPT2_UNICODE has no tables (bpe_gpu_split_preset)");
     if (preset != BPE_SPLIT_WORDS) return fail(BPE_GPU_EINVAL, "split_rule: no such preset");
     for (int b = 0; b < 256; b++)
         cls[b] = (b >= 'A' && b <= 'Z') || (b >= 'a' && b <= 'z') || b >= 0x80 ? 1
@@ -3501,7 +3503,7 @@ static uint32_t sx_grid(uint64_t items) {
 
 // The special passes of a split, between the marking kernel and the count scan (special.hip): find, and when
 // there are matches patch, recount and sort.  *M matches, *sorted their list by start (scratch slot 41).
-static int sp_mark(bpe_gpu_ctx *c, const SpSet *sp, bool gpt2, uint64_t n, uint64_t ntiles, uint32_t grid, uint16_t *mask,
+static int sp_mark(bpe_gpu_ctx *c, const SpSet *sp, int gpt2, uint64_t n, uint64_t ntiles, uint32_t grid, uint16_t *mask,
                    uint32_t *wcnt, uint32_t *M, unsigned long long **sorted, uint64_t *info) {
     int r;
     void *pset, *pcov, *pctl, *plist = nullptr, *psort, *tmp;
@@ -3533,7 +3535,7 @@ static int sp_mark(bpe_gpu_ctx *c, const SpSet *sp, bool gpt2, uint64_t n, uint6
     *sorted = nullptr;
     if (!found) return 0;
     k_sp_patch<<<sx_grid(found), SX_T, 0, c->st>>>(c->h.bytes, n, (const unsigned long long *)plist, found, (const SpSet *)pset,
-                                                  (const uint32_t *)pcov, (uint32_t *)mask, gpt2 ? 1 : 0);
+                                                  (const uint32_t *)pcov, (uint32_t *)mask, gpt2);
     HIPCHK(hipGetLastError());
     k_sp_recount<<<grid, SP_T, 0, c->st>>>(mask, ntiles, wcnt);
     HIPCHK(hipGetLastError());
@@ -3546,10 +3548,12 @@ static int sp_mark(bpe_gpu_ctx *c, const SpSet *sp, bool gpt2, uint64_t n, uint6
     return 0;
 }
 
-// the body of bpe_gpu_split (R: the tables) and of bpe_gpu_split_preset's BPE_SPLIT_GPT2 (R == nullptr): all but
+// the body of bpe_gpu_split (R: the tables) and of bpe_gpu_split_preset's BPE_SPLIT_GPT2 and BPE_SPLIT_GPT2_UNICODE
+// (R == nullptr; gpt2: 1 the first, 2 the second; sp_mark hands it to k_sp_patch): all but
 // the marking launch is one code, so the offsets and their lifetime are the same whichever kernel marked the starts.
 // sp: the specials of bpe_gpu_split_special (nullptr: none, and nothing but the launches below runs)
-static int split_run(bpe_gpu_ctx *c, const SplitRule *R, size_t *ndocs, const SpSet *sp = nullptr) {
+static int split_run(bpe_gpu_ctx *c, const SplitRule *R, size_t *ndocs, const SpSet *sp = nullptr, int gpt2 = 0) {
+    if (!R && !gpt2) gpt2 = 1;
     HIPCHK(hipSetDevice(c->dev));
     c->split_ready = false;
     c->ts_ready = false;  // bpe_gpu_train_split's results describe the offsets replaced here
@@ -3578,11 +3582,13 @@ static int split_run(bpe_gpu_ctx *c, const SplitRule *R, size_t *ndocs, const Sp
             k_split_table<<<SP_TBL / SP_T, SP_T, 0, c->st>>>(*R, (uint32_t *)tbl);
             HIPCHK(hipGetLastError());
             k_split_mark<<<grid, SP_T, 0, c->st>>>(c->h.bytes, n, (const uint32_t *)tbl, ntiles, mask, wcnt);
+        } else if (gpt2 == 2) {
+            k_split_mark_gpt2u<<<grid, SP_T, 0, c->st>>>(c->h.bytes, n, ntiles, mask, wcnt);
         } else {
             k_split_mark_gpt2<<<grid, SP_T, 0, c->st>>>(c->h.bytes, n, ntiles, mask, wcnt);
         }
         HIPCHK(hipGetLastError());
-        if (sp && (r = sp_mark(c, sp, R == nullptr, n, ntiles, grid, mask, wcnt, &sp_M, &sp_sorted, sp_info))) return r;
+        if (sp && (r = sp_mark(c, sp, R ? 0 : gpt2, n, ntiles, grid, mask, wcnt, &sp_M, &sp_sorted, sp_info))) return r;
         size_t tb = 0;
         HIPCHK(rocprim::exclusive_scan(nullptr, tb, wcnt, woff, 0ull, nwt + 1, rocprim::plus<unsigned long long>(), c->st));
         if ((r = dscratch(c, 15, tb, &tmp))) return r;
@@ -3653,11 +3659,11 @@ int bpe_gpu_split(bpe_gpu_ctx *c, const uint8_t *cls, const uint16_t *brk, size_
 
 int bpe_gpu_split_preset(bpe_gpu_ctx *c, int preset, size_t *ndocs) {
     if (!c || !ndocs) return BPE_GPU_EINVAL;
-    if (preset != BPE_SPLIT_LINES && preset != BPE_SPLIT_WORDS && preset != BPE_SPLIT_GPT2)
+    if (preset != BPE_SPLIT_LINES && preset != BPE_SPLIT_WORDS && preset != BPE_SPLIT_GPT2 && preset != BPE_SPLIT_GPT2_UNICODE)
         return fail(BPE_GPU_EINVAL, "split_preset: no such preset");
-    if (preset == BPE_SPLIT_GPT2) {
+    if (preset == BPE_SPLIT_GPT2 || preset == BPE_SPLIT_GPT2_UNICODE) {
         if (!c->loaded) return fail(BPE_GPU_ESTATE, "split before load");
-        return split_run(c, nullptr, ndocs);
+        return split_run(c, nullptr, ndocs, nullptr, preset == BPE_SPLIT_GPT2 ? 1 : 2);
     }
     uint8_t cls[256];
     uint16_t brk[16];
@@ -3669,7 +3675,8 @@ int bpe_gpu_split_special(bpe_gpu_ctx *c, int preset, const uint8_t *cls, const 
                           const bpe_gpu_specials *specials, size_t *ndocs) {
     if (!c || !ndocs) return BPE_GPU_EINVAL;
     if (preset < 0 && (!cls || !brk)) return fail(BPE_GPU_EINVAL, "split_special: no preset and no tables");
-    if (preset >= 0 && preset != BPE_SPLIT_LINES && preset != BPE_SPLIT_WORDS && preset != BPE_SPLIT_GPT2)
+    if (preset >= 0 && preset != BPE_SPLIT_LINES && preset != BPE_SPLIT_WORDS && preset != BPE_SPLIT_GPT2 &&
+        preset != BPE_SPLIT_GPT2_UNICODE)
         return fail(BPE_GPU_EINVAL, "split_special: no such preset");
     char msg[400];
     if (bpe_specials_check(specials, msg, sizeof msg)) return fail(BPE_GPU_EINVAL, msg);
@@ -3700,7 +3707,8 @@ int bpe_gpu_split_special(bpe_gpu_ctx *c, int preset, const uint8_t *cls, const 
     }
     H.S = (uint32_t)S;
     SplitRule R;
-    if (preset == BPE_SPLIT_GPT2) return split_run(c, nullptr, ndocs, &H);
+    if (preset == BPE_SPLIT_GPT2) return split_run(c, nullptr, ndocs, &H, 1);
+    if (preset == BPE_SPLIT_GPT2_UNICODE) return split_run(c, nullptr, ndocs, &H, 2);
     if (preset >= 0) {
         uint8_t pc[256];
         const int r = bpe_gpu_split_rule(preset, pc, R.brk);

@@ -15,7 +15,8 @@
 //                 bit e (e < n).  For BPE_SPLIT_GPT2 the positions s - 1 and e + 1 .. e + 3 outside any
 //                 match are decided again by the scalar form of the rule below over the window the
 //                 definition substitutes; a byte right after a match byte begins a segment and is a
-//                 start whatever the rule says.  Two matches may touch one mask word and may decide the same
+//                 start whatever the rule says.  For BPE_SPLIT_GPT2_UNICODE the positions are s - 7 .. s - 1
+//                 and e + 1 .. e + 6 and the rule is split.hip's su_starts over b[i - 7 .. i + 7].  Two matches may touch one mask word and may decide the same
 //                 position: every write is an atomicOr or atomicAnd of bits whose value is a function
 //                 of the bytes and the (complete) cover bitmap alone, so the order does not matter.
 //   k_sp_recount  the per-1,024-byte counts again from the masks: the scan and k_split_emit run as they are.
@@ -160,6 +161,32 @@ __device__ inline uint32_t sx_gpt2_start(const uint32_t *w) {
     return c != p;
 }
 
+// ---- BPE_SPLIT_GPT2_UNICODE for one position i (0 < i < n, neither i nor i - 1 a match byte): the rule of
+// split.hip's su_starts, one evaluation for the marking kernel and the patch, over b[i - 7 .. i + 7] as the
+// definition substitutes them before decoding.  Looking back, everything at or before the nearest match byte or
+// the start of the text reads as a newline; looking ahead, everything from the nearest match byte or n on reads
+// as a space (the segment ends there).  i is window byte 8; the window bytes the rule does not read are spaces.
+__device__ inline uint32_t sx_gpt2u_start(const uint8_t *__restrict__ bytes, uint64_t n, const uint32_t *__restrict__ cover,
+                                          uint64_t i) {
+    uint32_t w[8] = {0x20202020u, 0x20202020u, (uint32_t)bytes[i] | 0x20202000u, 0x20202020u,
+                     0x20202020u, 0x20202020u, 0x20202020u, 0x20202020u};
+    bool cut = false;
+#pragma unroll
+    for (uint32_t d = 1; d <= 7; d++) {
+        cut = cut || i < d || sx_covered(cover, i - d);
+        const uint32_t b = cut ? (uint32_t)'\n' : (uint32_t)bytes[i - d], q = 8u - d, sh = 8u * (q & 3u);
+        w[q >> 2] = (w[q >> 2] & ~(0xFFu << sh)) | (b << sh);
+    }
+    cut = false;
+#pragma unroll
+    for (uint32_t d = 1; d <= 7; d++) {
+        cut = cut || i + d >= n || sx_covered(cover, i + d);
+        const uint32_t b = cut ? (uint32_t)' ' : (uint32_t)bytes[i + d], q = 8u + d, sh = 8u * (q & 3u);
+        w[q >> 2] = (w[q >> 2] & ~(0xFFu << sh)) | (b << sh);
+    }
+    return (su_starts(w) >> 8) & 1u;
+}
+
 __global__ __launch_bounds__(SX_T) void k_sp_patch(const uint8_t *__restrict__ bytes, uint64_t n,
                                                    const unsigned long long *__restrict__ list, uint32_t M,
                                                    const SpSet *__restrict__ set, const uint32_t *__restrict__ cover,
@@ -174,6 +201,18 @@ __global__ __launch_bounds__(SX_T) void k_sp_patch(const uint8_t *__restrict__ b
         atomicOr(&mask32[s >> 5], 1u << (s & 31u));
         if (e < n) atomicOr(&mask32[e >> 5], 1u << (e & 31u));
         if (!gpt2) continue;
+        if (gpt2 == 2) {  // BPE_SPLIT_GPT2_UNICODE: s - 7 .. s - 1 and e + 1 .. e + 6 (e itself is set above)
+#pragma unroll 1
+            for (uint32_t k = 0; k < 13; k++) {
+                if (k < 7 && s + k < 7) continue;
+                const uint64_t i = k < 7 ? s + k - 7 : e + (uint64_t)(k - 6);
+                if (i >= n || sx_covered(cover, i)) continue;
+                const uint32_t v = i && !sx_covered(cover, i - 1) ? sx_gpt2u_start(bytes, n, cover, i) : 1u;
+                if (v) atomicOr(&mask32[i >> 5], 1u << (i & 31u));
+                else atomicAnd(&mask32[i >> 5], ~(1u << (i & 31u)));
+            }
+            continue;
+        }
 #pragma unroll
         for (int k = 0; k < 4; k++) {
             if (k == 0 && s == 0) continue;

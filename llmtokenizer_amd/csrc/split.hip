@@ -18,6 +18,11 @@
 //                  express: a start is a function of b[i - 4 .. i + 1] and n,
 //                  evaluated four bytes at a time with word arithmetic, no
 //                  table and no LDS; writes exactly what k_split_mark writes;
+//   k_split_mark_gpt2u  the same pass for BPE_SPLIT_GPT2_UNICODE: a start is a function
+//                  of b[i - 7 .. i + 7] and n; a wave whose windows are all ASCII runs
+//                  k_split_mark_gpt2's body, any other decodes UTF-8 and looks the
+//                  classes up in the two-stage table of unicode_classes.h (12.5 KiB,
+//                  read through the cache);
 //   (rocprim::exclusive_scan of the wave counts, engine.hip)
 //   k_split_emit   reads the masks again (n / 8 bytes, not the bytes): a wave
 //                  ranks its starts, stages their positions in LDS and writes
@@ -25,6 +30,9 @@
 //
 // No workgroup waits for another one: the order comes from the scan between
 // the two launches.
+
+#define BPE_UC_STORAGE __device__ const
+#include "unicode_classes.h"  // BPE_UC_STAGE1 / BPE_UC_STAGE2 in device memory
 
 namespace bpeamd {
 
@@ -115,35 +123,30 @@ __device__ inline uint32_t sg_in(uint32_t x, uint32_t lo, uint32_t hi) { return 
 __device__ inline uint32_t sg_up(uint32_t w, uint32_t lo, uint32_t k) { return __builtin_amdgcn_alignbit(w, lo, 32u - 8u * k); }
 __device__ inline uint32_t sg_dn(uint32_t w, uint32_t hi, uint32_t k) { return __builtin_amdgcn_alignbit(hi, w, 8u * k); }
 
-// what k_split_mark writes (the same tiles, grid striding, masks and counts), for the rule above
-__global__ __launch_bounds__(SP_T) void k_split_mark_gpt2(const uint8_t *__restrict__ bytes, uint64_t n, uint64_t ntiles,
-                                                          uint16_t *__restrict__ mask, uint32_t *__restrict__ wcnt) {
-    constexpr uint32_t SPACES = 0x20202020u, B7 = 0x80808080u;
-    const uint32_t tid = threadIdx.x, lane = tid & 63u;
-    // (the buffer has 64 bytes of slack past n: a load that begins below n stays inside it)
-    auto load16 = [&](uint64_t tile) {
-        const uint64_t o = (tile * SP_T + tid) * SP_PER;
-        if (tile >= ntiles || o >= n) return make_uint4(SPACES, SPACES, SPACES, SPACES);
-        uint4 v = *(const uint4 *)(bytes + o);
-        if (n - o < SP_PER) {  // the text ends inside these 16 bytes
-            const uint32_t r = (uint32_t)(n - o);
-            uint32_t x[4] = {v.x, v.y, v.z, v.w};
+// a thread's 16 bytes of a tile with every byte at or past n replaced by a space (all spaces past the tiles)
+// (the buffer has 64 bytes of slack past n: a load that begins below n stays inside it)
+__device__ inline uint4 sg_load16(const uint8_t *__restrict__ bytes, uint64_t n, uint64_t ntiles, uint64_t tile) {
+    constexpr uint32_t SPACES = 0x20202020u;
+    const uint64_t o = (tile * SP_T + threadIdx.x) * SP_PER;
+    if (tile >= ntiles || o >= n) return make_uint4(SPACES, SPACES, SPACES, SPACES);
+    uint4 v = *(const uint4 *)(bytes + o);
+    if (n - o < SP_PER) {  // the text ends inside these 16 bytes
+        const uint32_t r = (uint32_t)(n - o);
+        uint32_t x[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
-            for (uint32_t j = 0; j < 4; j++) {
-                const uint32_t keep = r <= 4 * j ? 0u : r - 4 * j >= 4 ? ~0u : (1u << (8 * (r - 4 * j))) - 1u;
-                x[j] = (x[j] & keep) | (SPACES & ~keep);
-            }
-            v = make_uint4(x[0], x[1], x[2], x[3]);
+        for (uint32_t j = 0; j < 4; j++) {
+            const uint32_t keep = r <= 4 * j ? 0u : r - 4 * j >= 4 ? ~0u : (1u << (8 * (r - 4 * j))) - 1u;
+            x[j] = (x[j] & keep) | (SPACES & ~keep);
         }
-        return v;
-    };
-    uint4 q = load16(blockIdx.x);
-    for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const uint64_t t = tile * SP_T + tid, o = t * SP_PER;
-        const uint4 qn = load16(tile + gridDim.x);
-        uint32_t w[6] = {__shfl_up(q.w, 1), q.x, q.y, q.z, q.w, __shfl_down(q.x, 1)};
-        if (lane == 0) w[0] = o && o < n ? *(const uint32_t *)(bytes + o - 4) : 0x0A0A0A0Au;  // (o is a multiple of 16)
-        if (lane == 63) w[5] = o + SP_PER < n ? (uint32_t)bytes[o + SP_PER] : SPACES;
+        v = make_uint4(x[0], x[1], x[2], x[3]);
+    }
+    return v;
+}
+
+// the 16 start bits of a thread's bytes from its six words (before byte 0 and the end of the text are applied)
+__device__ inline uint32_t sg_mark16(const uint32_t *w) {
+    constexpr uint32_t SPACES = 0x20202020u, B7 = 0x80808080u;
+    {
         // per word: L letters, N digits, ws white space, S the space, ap the apostrophe; m1 one of s t m d,
         // rv one of r v, e, l (the letters of the contractions)
         uint32_t L[6], N[6], ws[6], S[6], ap[6], m1[6], rv[6], e[6], l[6];
@@ -185,6 +188,145 @@ __global__ __launch_bounds__(SP_T) void k_split_mark_gpt2(const uint8_t *__restr
             // bits 7, 15, 23, 31 -> 0, 1, 2, 3
             m |= (((st >> 7) | (st >> 14) | (st >> 21) | (st >> 28)) & 15u) << (4 * (j - 1));
         }
+        return m;
+    }
+}
+
+// what k_split_mark writes (the same tiles, grid striding, masks and counts), for the rule above
+__global__ __launch_bounds__(SP_T) void k_split_mark_gpt2(const uint8_t *__restrict__ bytes, uint64_t n, uint64_t ntiles,
+                                                          uint16_t *__restrict__ mask, uint32_t *__restrict__ wcnt) {
+    constexpr uint32_t SPACES = 0x20202020u;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    uint4 q = sg_load16(bytes, n, ntiles, blockIdx.x);
+    for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const uint64_t t = tile * SP_T + tid, o = t * SP_PER;
+        const uint4 qn = sg_load16(bytes, n, ntiles, tile + gridDim.x);
+        uint32_t w[6] = {__shfl_up(q.w, 1), q.x, q.y, q.z, q.w, __shfl_down(q.x, 1)};
+        if (lane == 0) w[0] = o && o < n ? *(const uint32_t *)(bytes + o - 4) : 0x0A0A0A0Au;  // (o is a multiple of 16)
+        if (lane == 63) w[5] = o + SP_PER < n ? (uint32_t)bytes[o + SP_PER] : SPACES;
+        uint32_t m = sg_mark16(w);
+        if (o == 0) m |= 1u;  // byte 0 starts a piece
+        m = o >= n ? 0u : n - o >= SP_PER ? m : m & ((1u << (uint32_t)(n - o)) - 1u);
+        mask[t] = (uint16_t)m;
+        uint32_t c = (uint32_t)__builtin_popcount(m);
+        for (int d = 32; d; d >>= 1) c += __shfl_xor(c, d);
+        if (lane == 0) wcnt[t >> 6] = c;
+        q = qn;
+    }
+}
+
+// ---- BPE_SPLIT_GPT2_UNICODE (bpe_gpu.h): the same rule over the characters of the text decoded as UTF-8; a start
+// is a function of b[i - 7 .. i + 7] and n.
+//
+// A thread's window is eight words, w[0..7] = b[o - 8 .. o + 23]: window byte q is b[o - 8 + q].  Here every
+// predicate is one 32-bit mask over the window, bit q for byte q, so "the byte k before / after" is a shift and
+// the rule is evaluated for all of a thread's bytes (q = 8 .. 23) at once.  The ASCII predicates are classified
+// four bytes at a time as above and gathered into the masks.  Every window byte 1 .. 27 is then decoded as the
+// lead of a UTF-8 sequence from the four bytes that begin there (well-formedness at q is a function of those
+// alone): a well-formed lead gives its class, looked up in the two-stage table of unicode_classes.h, to all
+// bytes of its sequence and marks the others as continuation bytes; a byte >= 0x80 in no sequence stays in no
+// mask: class P.  A sequence that begins at q = 0 is not seen, which misreads q <= 3 at most, and bit q of the
+// result reads class bits from q - 4 on.  No branch and no loop depends on the text: a byte that leads
+// nothing looks up code point 0.
+
+// bits 7, 15, 23, 31 of x -> bits 0..3
+__device__ inline uint32_t su_nib(uint32_t x) {
+    x &= 0x80808080u;
+    return ((x >> 7) | (x >> 14) | (x >> 21) | (x >> 28)) & 15u;
+}
+
+// bit q: a piece starts at window byte q (valid for q = 8 .. 23; byte 0 of the text and its end are the caller's)
+__device__ inline uint32_t su_starts(const uint32_t *w) {
+    constexpr uint32_t SPACES = 0x20202020u, B7 = 0x80808080u;
+    // L letters, N numbers, ws white space, S the space, ap the apostrophe; m1 one of s t m d, rv one of r v, e, l
+    uint32_t L = 0, N = 0, ws = 0, S = 0, ap = 0, m1 = 0, rv = 0, e = 0, l = 0;
+#pragma unroll
+    for (uint32_t j = 0; j < 8; j++) {
+        const uint32_t hi = w[j] & B7;
+        const uint32_t x = (w[j] & ~B7) | (hi - (hi >> 7));  // a byte >= 0x80 becomes 0x7f: in none of the ranges below
+        const uint32_t s = sg_in(x, ' ', ' ');
+        S |= su_nib(s) << (4 * j);
+        ws |= su_nib(s | sg_in(x, '\t', '\r')) << (4 * j);
+        L |= su_nib(sg_in(x | SPACES, 'a', 'z')) << (4 * j);
+        N |= su_nib(sg_in(x, '0', '9')) << (4 * j);
+        ap |= su_nib(sg_in(x, '\'', '\'')) << (4 * j);
+        m1 |= su_nib(sg_in(x, 'd', 'd') | sg_in(x, 'm', 'm') | sg_in(x, 's', 't')) << (4 * j);
+        rv |= su_nib(sg_in(x, 'r', 'r') | sg_in(x, 'v', 'v')) << (4 * j);
+        e |= su_nib(sg_in(x, 'e', 'e')) << (4 * j);
+        l |= su_nib(sg_in(x, 'l', 'l')) << (4 * j);
+    }
+    // cont: continuation bytes of well-formed sequences; w2 / w3: leads of white space of two / three bytes
+    uint32_t cont = 0, w2 = 0, w3 = 0;
+#pragma unroll
+    for (uint32_t q = 1; q <= 27; q++) {
+        const uint32_t v = q & 3u ? __builtin_amdgcn_alignbit(w[(q >> 2) + 1], w[q >> 2], 8u * (q & 3u)) : w[q >> 2];
+        const uint32_t b0 = v & 0xFFu, b1 = (v >> 8) & 0x3Fu, b2 = (v >> 16) & 0x3Fu, b3 = (v >> 24) & 0x3Fu;
+        const uint32_t cp2 = ((b0 & 0x1Fu) << 6) | b1, cp3 = ((b0 & 0x0Fu) << 12) | (b1 << 6) | b2;
+        const uint32_t cp4 = ((b0 & 0x07u) << 18) | (b1 << 12) | (b2 << 6) | b3;
+        // Unicode Table 3-7: E0 A0..BF is cp3 >= 0x800, ED 80..9F is no surrogate, F0 90..BF is cp4 >= 0x10000,
+        // F4 80..8F and no lead above F4 is cp4 <= 0x10FFFF
+        const bool ok2 = b0 >= 0xC2u && b0 <= 0xDFu && (v & 0xC000u) == 0x8000u;
+        const bool ok3 = (b0 & 0xF0u) == 0xE0u && (v & 0xC0C000u) == 0x808000u && cp3 >= 0x800u && (cp3 & 0xF800u) != 0xD800u;
+        const bool ok4 = (b0 & 0xF8u) == 0xF0u && (v & 0xC0C0C000u) == 0x80808000u && cp4 >= 0x10000u && cp4 <= 0x10FFFFu;
+        const uint32_t len = ok2 ? 2u : ok3 ? 3u : ok4 ? 4u : 0u;
+        const uint32_t cp = ok2 ? cp2 : ok3 ? cp3 : ok4 ? cp4 : 0u;
+        const uint32_t t = (BPE_UC_STAGE2[16u * BPE_UC_STAGE1[cp >> 8] + ((cp >> 4) & 15u)] >> (2u * (cp & 15u))) & 3u;
+        const uint32_t rng = ((1u << len) - 1u) << q;  // the bytes of the sequence (none when nothing is led here)
+        L |= t == 1u ? rng : 0u;
+        N |= t == 2u ? rng : 0u;
+        ws |= t == 3u ? rng : 0u;
+        cont |= rng & (rng - 1u);
+        w2 |= t == 3u && len == 2u ? 1u << q : 0u;
+        w3 |= t == 3u && len == 3u ? 1u << q : 0u;
+        if (q % 9u == 0u) __builtin_amdgcn_sched_barrier(0);  // nine lookups in flight at a time: the registers of 27 are not there
+    }
+    const uint32_t ws1 = ws << 1, S1 = S << 1;
+    // the class at end(i) is white space (no white space has four bytes)
+    const uint32_t wsn = ((ws >> 1) & ~(w2 | w3)) | ((ws >> 2) & w2) | ((ws >> 3) & w3);
+    const uint32_t a = ap & ((L | N | (ws & ~S)) << 1);  // an apostrophe a contraction may start at
+    const uint32_t c2 = a & (m1 >> 1), c3 = a & (((rv >> 1) & (e >> 2)) | ((l >> 1) & (l >> 2)));
+    const uint32_t inside = ((c2 | c3) << 1) | (c3 << 2), after = (c2 << 2) | (c3 << 3);
+    const uint32_t diff = (L ^ (L << 1)) | (N ^ (N << 1));
+    const uint32_t text = (ws1 & ~S1) | ((after | diff) & ~(ws1 | inside));  // b[i] is not white space
+    return ((ws & ~(ws1 & wsn)) | (~ws & text)) & ~cont;
+}
+
+// what k_split_mark writes, for BPE_SPLIT_GPT2_UNICODE.  The two words before a thread's 16 bytes come from the
+// lane below and the two after them from the lane above; lanes 0 and 63 load theirs, only below n.  Bytes at and
+// past n read as spaces and the bytes before byte 0 as newlines before anything is decoded, so a sequence the
+// end cuts is ill-formed.  A wave none of whose windows holds a byte >= 0x80 runs k_split_mark_gpt2's body.
+__global__ __launch_bounds__(SP_T) void k_split_mark_gpt2u(const uint8_t *__restrict__ bytes, uint64_t n, uint64_t ntiles,
+                                                           uint16_t *__restrict__ mask, uint32_t *__restrict__ wcnt) {
+    constexpr uint32_t SPACES = 0x20202020u, B7 = 0x80808080u;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u;
+    uint4 q = sg_load16(bytes, n, ntiles, blockIdx.x);
+    for (uint64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const uint64_t t = tile * SP_T + tid, o = t * SP_PER;
+        const uint4 qn = sg_load16(bytes, n, ntiles, tile + gridDim.x);
+        uint32_t w[8] = {__shfl_up(q.z, 1), __shfl_up(q.w, 1), q.x, q.y, q.z, q.w, __shfl_down(q.x, 1), __shfl_down(q.y, 1)};
+        if (lane == 0) {  // (o is a multiple of 16: b[o - 8 .. o - 1] lie below n when o does)
+            const uint2 v = o && o < n ? *(const uint2 *)(bytes + o - 8) : make_uint2(0x0A0A0A0Au, 0x0A0A0A0Au);
+            w[0] = v.x;
+            w[1] = v.y;
+        }
+        if (lane == 63) {
+            uint2 v = make_uint2(SPACES, SPACES);
+            if (o + SP_PER < n) {  // (a load that begins below n stays inside the slack)
+                v = *(const uint2 *)(bytes + o + SP_PER);
+                const uint64_t r = n - (o + SP_PER);  // bytes of text in it
+                if (r < 8) {
+                    const uint32_t r4 = (uint32_t)r & 3u, keep = (1u << (8u * r4)) - 1u;  // (r4 == 0: keep nothing)
+                    if (r < 4) v = make_uint2((v.x & keep) | (SPACES & ~keep), SPACES);
+                    else v.y = (v.y & keep) | (SPACES & ~keep);
+                }
+            }
+            w[6] = v.x;
+            w[7] = v.y;
+        }
+        const bool high = ((w[0] | w[1] | w[2] | w[3] | w[4] | w[5] | w[6] | w[7]) & B7) != 0u;
+        uint32_t m;
+        if (__ballot(high) == 0ull) m = sg_mark16(w + 1);  // (what lies past byte 0 of its last word decides none of these 16 bits)
+        else m = (su_starts(w) >> 8) & 0xFFFFu;
         if (o == 0) m |= 1u;  // byte 0 starts a piece
         m = o >= n ? 0u : n - o >= SP_PER ? m : m & ((1u << (uint32_t)(n - o)) - 1u);
         mask[t] = (uint16_t)m;

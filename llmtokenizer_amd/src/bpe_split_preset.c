@@ -5,6 +5,7 @@
  * bpe_gpu_split_preset, on the bodies bpe_encode_split and bpe_train_split run.
  */
 #include "bpe_internal.h"
+#include "../csrc/unicode_classes.h"
 
 enum { C_P = 0, C_L = 1, C_N = 2, C_S = 3, C_W = 4 }; /* the classes of BPE_SPLIT_WORDS and BPE_SPLIT_GPT2 */
 
@@ -49,6 +50,99 @@ static int starts_gpt2(const uint8_t *b, size_t n, size_t i)
     return c != p;
 }
 
+/* ---- BPE_SPLIT_GPT2_UNICODE: the same rule over the characters of the text decoded as UTF-8 */
+
+int bpe_unicode_class(uint32_t cp)
+{
+    if (cp == 0x20) return C_S;
+    if (cp > 0x10FFFF) return C_P;
+    const uint32_t t = (BPE_UC_STAGE2[16u * BPE_UC_STAGE1[cp >> 8] + ((cp >> 4) & 15u)] >> (2u * (cp & 15u))) & 3u;
+    return t == 3 ? C_W : (int)t;
+}
+
+int bpe_unicode_info(const char **source, uint64_t *digest)
+{
+    if (source) *source = BPE_UC_SOURCE;
+    if (digest) *digest = BPE_UC_DIGEST;
+    return 0;
+}
+
+/* the length (1..4) of the well-formed UTF-8 sequence (Unicode Table 3-7) that b[i ..] begins inside the
+ * text, *cp its code point; 0 when there is none: an overlong form, a surrogate, a value above U+10FFFF,
+ * a sequence the end of the text cuts, a byte that leads nothing */
+static int u8_seq(const uint8_t *b, size_t n, size_t i, uint32_t *cp)
+{
+    const uint32_t b0 = b[i];
+    if (b0 < 0x80) {
+        *cp = b0;
+        return 1;
+    }
+    const int len = b0 >= 0xC2 && b0 <= 0xDF ? 2 : b0 >= 0xE0 && b0 <= 0xEF ? 3 : b0 >= 0xF0 && b0 <= 0xF4 ? 4 : 0;
+    if (!len || n - i < (size_t)len) return 0;
+    uint32_t v = b0 & (0x7Fu >> len);
+    for (int k = 1; k < len; k++) {
+        if ((b[i + k] & 0xC0) != 0x80) return 0;
+        v = (v << 6) | (b[i + k] & 0x3Fu);
+    }
+    if ((len == 3 && (v < 0x800 || (v >= 0xD800 && v <= 0xDFFF))) || (len == 4 && (v < 0x10000 || v > 0x10FFFF))) return 0;
+    *cp = v;
+    return len;
+}
+
+/* the character byte i < n belongs to: its class, *start its first byte and *end the offset just past it.
+ * A byte in no well-formed sequence is a character of its own with class P. */
+static int char_at(const uint8_t *b, size_t n, size_t i, size_t *start, size_t *end)
+{
+    uint32_t cp = 0;
+    for (size_t d = 0; d <= 3 && d <= i; d++) { /* (a lead byte never lies inside another sequence: at most one d fits) */
+        const int len = u8_seq(b, n, i - d, &cp);
+        if ((size_t)len > d) {
+            if (start) *start = i - d;
+            if (end) *end = i - d + (size_t)len;
+            return bpe_unicode_class(cp);
+        }
+        if (d == 0 && (b[i] & 0xC0) != 0x80) break; /* no continuation byte: nothing before it holds it */
+    }
+    if (start) *start = i;
+    if (end) *end = i + 1;
+    return C_P;
+}
+
+/* clen with the class of the character before the apostrophe (the contractions themselves are ASCII) */
+static int clen_u(const uint8_t *b, size_t n, size_t j)
+{
+    if (b[j] != '\'' || j + 1 >= n) return 0;
+    if (j) {
+        const int p = char_at(b, n, j - 1, NULL, NULL);
+        if (p != C_L && p != C_N && p != C_W) return 0;
+    }
+    const uint8_t x = b[j + 1];
+    if (x == 's' || x == 't' || x == 'm' || x == 'd') return 2;
+    if (j + 2 >= n) return 0;
+    const uint8_t y = b[j + 2];
+    return ((x == 'r' || x == 'v') && y == 'e') || (x == 'l' && y == 'l') ? 3 : 0;
+}
+
+/* does a piece start at byte i, 0 < i < n? */
+static int starts_gpt2u(const uint8_t *b, size_t n, size_t i)
+{
+    size_t st, en;
+    const int c = char_at(b, n, i, &st, &en);
+    if (st != i) return 0; /* a continuation byte */
+    const int p = char_at(b, n, i - 1, NULL, NULL);
+    const int cw = c == C_S || c == C_W, pw = p == C_S || p == C_W;
+    if (cw) {
+        if (!pw) return 1;
+        if (en >= n) return 0;
+        const int x = char_at(b, n, en, NULL, NULL); /* (the character that begins at end(i)) */
+        return x != C_S && x != C_W;
+    }
+    if (pw) return p == C_W;
+    if (clen_u(b, n, i - 1) >= 2 || (i >= 2 && clen_u(b, n, i - 2) == 3)) return 0;
+    if ((i >= 2 && clen_u(b, n, i - 2) == 2) || (i >= 3 && clen_u(b, n, i - 3) == 3)) return 1;
+    return c != p;
+}
+
 static int starts_words(const uint8_t *b, size_t i)
 {
     const int c = class_of(b[i]), p = class_of(b[i - 1]);
@@ -58,10 +152,12 @@ static int starts_words(const uint8_t *b, size_t i)
 int bpe_split_offsets_host(int preset, const uint8_t *bytes, size_t n, uint64_t *out, size_t cap, size_t *count)
 {
     if ((!bytes && n) || !count) return BPE_GPU_EINVAL;
-    if (preset != BPE_SPLIT_LINES && preset != BPE_SPLIT_WORDS && preset != BPE_SPLIT_GPT2) return BPE_GPU_EINVAL;
+    if (preset != BPE_SPLIT_LINES && preset != BPE_SPLIT_WORDS && preset != BPE_SPLIT_GPT2 && preset != BPE_SPLIT_GPT2_UNICODE)
+        return BPE_GPU_EINVAL;
     size_t k = 0;
     for (size_t i = 0; i < n; i++) {
         const int s = i == 0                     ? 1
+                      : preset == BPE_SPLIT_GPT2_UNICODE ? starts_gpt2u(bytes, n, i)
                       : preset == BPE_SPLIT_GPT2 ? starts_gpt2(bytes, n, i)
                       : preset == BPE_SPLIT_WORDS ? starts_words(bytes, i)
                                                   : bytes[i - 1] == '\n';

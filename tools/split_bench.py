@@ -5,7 +5,10 @@ encode_split against the host-offset path it replaces.
 Two 1 GiB corpora resident in HBM: the seed-3 synthetic corpus (Engine.synth;
 printable bytes, no newline) and english_like (a 32 MiB sample generated on the
 host and repeated to the size).  Three rules: the table rules "lines" and
-"words", and "gpt2" (bpe_gpu_split_preset; its own marking kernel).
+"words", and "gpt2" and "gpt2_unicode" (bpe_gpu_split_preset; their own marking
+kernels).  A third corpus, english_nonascii, is english_like with every
+--nonascii-th letter replaced by a two-byte Cyrillic letter (D0 B0..BF): the
+ASCII corpora take gpt2_unicode's all-ASCII path, this one its decoding path.
 
   split    Engine.split(rule) alone, alternated with a device-to-device
            hipMemcpyAsync of the same number of bytes timed the same way (host
@@ -57,6 +60,22 @@ def restate(buf, cls, brk, chunk=1 << 25):
         prev = c[-1]
     parts.append(np.array([buf.size], dtype=np.uint64))
     return np.concatenate(parts)
+
+
+def nonascii(sample, every):
+    """sample with every `every`-th ASCII letter replaced by the two bytes D0, B0 + (letter & 15)"""
+    letters = np.flatnonzero(((sample | 0x20) >= ord("a")) & ((sample | 0x20) <= ord("z")))[::every]
+    width = np.ones(sample.size, np.int64)
+    width[letters] = 2
+    at = np.cumsum(width) - width
+    out = np.empty(int(width.sum()), np.uint8)
+    out[at] = sample
+    out[at[letters]] = 0xD0
+    out[at[letters] + 1] = 0xB0 + (sample[letters] & 15)
+    return out
+
+
+NO_TABLES = ("gpt2", "gpt2_unicode")
 
 
 def med(xs):
@@ -115,6 +134,10 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--sample", type=int, default=1 << 25, help="bytes of english_like generated, then repeated")
     ap.add_argument("--no-e2e", action="store_true", help="the split alone")
+    ap.add_argument("--rules", default="lines,words,gpt2,gpt2_unicode", help="the rules to run, comma separated")
+    ap.add_argument("--nonascii", type=int, default=4, help="english_nonascii: one letter in this many is two bytes")
+    ap.add_argument("--check-bytes", type=int, default=0,
+                    help="with --no-e2e: compare the device's offsets with split_host over this many leading bytes")
     ap.add_argument("--device", type=int, default=0)
     args = ap.parse_args()
     if api.device_count() < 1:
@@ -133,14 +156,15 @@ def main():
     cp = DeviceCopy(n)
     e = api.Engine(args.device)
     sample = np.frombuffer(english_like(min(args.sample, n)), np.uint8)
-    for corpus in ("seed3", "english_like"):
+    for corpus in ("seed3", "english_like", "english_nonascii"):
         if corpus == "seed3":
             e.synth(3, n)
             host = None
         else:
-            host = np.tile(sample, (n + sample.size - 1) // sample.size)[:n]
+            part = sample if corpus == "english_like" else nonascii(sample, args.nonascii)
+            host = np.tile(part, (n + part.size - 1) // part.size)[:n]
             e.load(host.tobytes())
-        for rule in ("lines", "words", "gpt2"):
+        for rule in args.rules.split(","):
             key = f"{corpus}/{rule}"
             nd = e.split(rule)  # warm
             cp.run()
@@ -160,11 +184,18 @@ def main():
                 "bytes_moved": int(moved), "algorithmic_bytes": int(n + 8 * (nd + 1)),
                 "gbps": round(rate, 1), "copy_gbps": round(copy_rate, 1), "over_copy": round(rate / copy_rate, 3)}
             if args.no_e2e:
+                if args.check_bytes and rule in NO_TABLES:
+                    k = min(args.check_bytes, n)
+                    head = synth_bytes(3, k) if host is None else host[:k].tobytes()
+                    want = api.split_host(head, rule)[:-16]  # (the last pieces of the head see its end)
+                    if not (e.split_offsets()[:want.size] == want).all():
+                        sys.exit(f"split_bench: {key}: the device's offsets differ from split_host")
+                    out["split"][key]["offsets_equal_split_host_over_bytes"] = int(want[-1])
                 continue
             if host is None:  # the parent path's user holds the text on the host
                 host = np.frombuffer(synth_bytes(3, n), np.uint8)
             t0 = time.perf_counter()
-            off = api.split_host(host, rule) if rule == "gpt2" else restate(host, *api.split_rule(rule))
+            off = api.split_host(host, rule) if rule in NO_TABLES else restate(host, *api.split_rule(rule))
             t_numpy = time.perf_counter() - t0
             if off.size - 1 != nd or not (e.split_offsets() == off).all():
                 sys.exit(f"split_bench: {key}: the device's offsets differ from the restatement")
@@ -194,7 +225,7 @@ def main():
             out["e2e"][key] = {
                 "pieces": int(nd), "resident": r, "resident_split_part": med(t_res_split),
                 "resident_encode_part": med([a - b for a, b in zip(t_res, t_res_split)]), "host_offsets": h,
-                "numpy_offsets_ms": round(t_numpy * 1e3, 1), "offsets_made_by": "split_host" if rule == "gpt2" else "numpy",
+                "numpy_offsets_ms": round(t_numpy * 1e3, 1), "offsets_made_by": "split_host" if rule in NO_TABLES else "numpy",
                 "single": s, "docs_info": info,
                 "resident_gbps": round(n / r["ms_median"] / 1e6, 2), "host_gbps": round(n / h["ms_median"] / 1e6, 2),
                 "host_with_numpy_gbps": round(n / (h["ms_median"] + t_numpy * 1e3) / 1e6, 3),
@@ -204,7 +235,7 @@ def main():
                 "single_spread": round((s["ms_max"] - s["ms_min"]) / s["ms_median"], 4)}
             del off
             print(json.dumps({"progress": key, **out["e2e"][key]}), file=sys.stderr, flush=True)
-        ab = {"words": [], "gpt2": []}
+        ab = {rule: [] for rule in ("words", "gpt2", "gpt2_unicode") if rule in args.rules.split(",")}
         for _ in range(reps):
             for rule, ts in ab.items():
                 t0 = time.perf_counter()
