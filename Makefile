@@ -118,3 +118,13 @@ tests/asan_split_unicode/asan_split_unicode: tests/asan_split_unicode/asan_split
 
 asan-split-unicode: tests/asan_split_unicode/asan_split_unicode
 .PHONY: asan-split-unicode
+
+# BPE_SPLIT_CL100K's host code (the rule in src/bpe_split_preset.c and the preset through src/bpe_special.c) the
+# same way, in a stand-alone program that calls no engine function (tests/asan_split_cl100k/asan_split_cl100k.c);
+# run by tests/test_asan_split_cl100k.py
+tests/asan_split_cl100k/asan_split_cl100k: tests/asan_split_cl100k/asan_split_cl100k.c $(CSRC_SPECIAL) $(CSRC_SP) $(wildcard include/*.h $(PKG)/src/*.h $(PKG)/csrc/unicode_classes.h)
+	$(CC) -O1 -g -std=c11 -D_GNU_SOURCE -fno-omit-frame-pointer -fsanitize=address,undefined \
+	    -fno-sanitize-recover=undefined -Iinclude -o $@ tests/asan_split_cl100k/asan_split_cl100k.c $(CSRC_SPECIAL) $(CSRC_SP) -lm
+
+asan-split-cl100k: tests/asan_split_cl100k/asan_split_cl100k
+.PHONY: asan-split-cl100k

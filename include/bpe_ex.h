@@ -74,7 +74,7 @@ uint32_t *bpe_encode_split(const uint8_t *bytes, size_t n, const uint8_t *cls, c
 dyn_arr_t *bpe_train_split(const uint8_t *bytes, size_t n, const uint8_t *cls, const uint16_t *brk, long max_merges,
                            int device);
 
-/* The preset split rules (bpe_gpu.h: BPE_SPLIT_LINES, BPE_SPLIT_WORDS, BPE_SPLIT_GPT2, BPE_SPLIT_GPT2_UNICODE) in plain C, on
+/* The preset split rules (bpe_gpu.h: BPE_SPLIT_LINES, BPE_SPLIT_WORDS, BPE_SPLIT_GPT2, BPE_SPLIT_GPT2_UNICODE, BPE_SPLIT_CL100K) in plain C, on
  * the host and without a GPU: the written definition bpe_gpu_split_preset is held to, and the
  * yardstick for inputs too large for a regular-expression engine.  Two-phase like the fetch calls:
  * out may be NULL, *count = pieces + 1 (the piece starts followed by n; n == 0: the single offset 0),

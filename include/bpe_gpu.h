@@ -321,8 +321,44 @@ int bpe_gpu_docs_window(const uint64_t *doc_off, size_t ndocs, uint64_t n,
  * So a start depends on b[i - 7 .. i + 7] and n alone, and on a window whose
  * bytes are all below 0x80 the rule equals BPE_SPLIT_GPT2.  Where this
  * formulation and the regular expression disagree the expression is the
- * definition.  cl100k's \p{N}{1,3} and case-insensitive contractions are other
- * patterns and not offered.
+ * definition.
+ *
+ * BPE_SPLIT_CL100K is the pre-tokenizer of cl100k_base and of Llama 3 (no table
+ * rule either).  Its pieces are the successive matches of
+ *   (?i:'s|'t|'re|'ve|'m|'ll|'d)|[^\r\n\p{L}\p{N}]?\p{L}+|\p{N}{1,3}| ?[^\s\p{L}\p{N}]+[\r\n]*|\s*[\r\n]+|\s+(?!\S)|\s+
+ * as the `regex` module (V0) finds them, reported as byte offsets, over the text
+ * decoded as BPE_SPLIT_GPT2_UNICODE decodes it: the same characters (a byte in no
+ * well-formed sequence is a character of class P), the same class table, and a
+ * continuation byte starts nothing.  Six classes: R is \r and \n, S is U+0020,
+ * W the other White_Space, L, N, and P the rest; "ws" is R, S or W.  Per
+ * character, with indices that count characters, c = K[i], p = K[i - 1]:
+ *   Character 0 starts a piece; before the text everything reads as R.
+ *   Contractions.  The apostrophe at j opens one when K[j - 1] is L, N, R or W.
+ *     clen(j) is then 2 when the next character folds to s, t, m or d, 3 when
+ *     the next two fold to re, ve or ll, and 0 otherwise or when the text ends
+ *     before them.  Folding maps A-Z to a-z and U+017F to s and nothing else, so
+ *     a contraction is 2, 3 or (with U+017F) 3 bytes for 2 characters.
+ *   c is N:   a start when (the index of i within its run of N) mod 3 is 0.
+ *   c is ws, p is not:  a start, unless p is P and c is R (the newlines right
+ *     after punctuation belong to its piece).
+ *   c is R, p is ws:    no start.
+ *   c is S or W, p is ws, q the end of this white-space run: a start when
+ *     (C) i == q - 1 and q < n, or
+ *     (B) p is R and no R occurs in [i, q), or
+ *     (A) p is R, every character from the run's first up to i - 1 is R, and the
+ *         character before the run is P.
+ *   c is L, the first that fits: no start when clen(i - 1) >= 2 or
+ *     clen(i - 2) == 3; a start when clen(i - 2) == 2 or clen(i - 3) == 3; no
+ *     start when p is L; a start when p is N or R; no start when p is S or W
+ *     (that character is the piece's prefix); when p is P, a start exactly when
+ *     K[i - 2] is P or S (the P then belongs to a punctuation piece).
+ *   c is P:   a start when p is L, N, R or W; no start when p is P or S.
+ * Three conditions reach through runs of any length: the index in a run of N,
+ * (A) back through a run of R, (B) ahead through white space.  The rest depends
+ * on b[i - 8 .. i + 7] and n.  Where this formulation and the regular expression
+ * disagree the expression is the definition.  bpe_ex.h's bpe_split_offsets_host
+ * is this rule in plain C, one pass from the left.  o200k's pattern (case classes)
+ * is another pattern and not offered.
  *
  * The offsets belong to the loaded bytes.  bpe_gpu_load / _load_fd / _synth /
  * _trim, bpe_gpu_train / _train_ex and a sharded group's load, synth and train
@@ -331,20 +367,20 @@ int bpe_gpu_docs_window(const uint64_t *doc_off, size_t ndocs, uint64_t n,
  * bpe_gpu_split replaces them.  A call that needs them and finds none returns
  * BPE_GPU_ESTATE.
  * ---------------------------------------------------------------------- */
-enum { BPE_SPLIT_LINES = 0, BPE_SPLIT_WORDS = 1, BPE_SPLIT_GPT2 = 2, BPE_SPLIT_GPT2_UNICODE = 4 }; /* (3 is no preset) */
+enum { BPE_SPLIT_LINES = 0, BPE_SPLIT_WORDS = 1, BPE_SPLIT_GPT2 = 2, BPE_SPLIT_GPT2_UNICODE = 4, BPE_SPLIT_CL100K = 6 }; /* (3 and 5 are no presets) */
 /* bytes one workgroup of the split kernels handles per step, and the largest grid
    (a corpus of more than TILE * GRID bytes is walked in grid strides) */
 #define BPE_GPU_SPLIT_TILE 4096
 #define BPE_GPU_SPLIT_GRID 2048
-/* fill cls[256] / brk[16] with a table preset (pure function, no GPU); BPE_SPLIT_GPT2 and BPE_SPLIT_GPT2_UNICODE
-   have no tables: BPE_GPU_EINVAL */
+/* fill cls[256] / brk[16] with a table preset (pure function, no GPU); BPE_SPLIT_GPT2, BPE_SPLIT_GPT2_UNICODE and
+   BPE_SPLIT_CL100K have no tables: BPE_GPU_EINVAL */
 int bpe_gpu_split_rule(int preset, uint8_t *cls, uint16_t *brk);
 /* out4 = {BPE_GPU_SPLIT_TILE, BPE_GPU_SPLIT_TILE * BPE_GPU_SPLIT_GRID, 0, 0} (pure function, no GPU) */
 int bpe_gpu_split_info(uint64_t *out4);
 /* split the loaded bytes; *ndocs = pieces.  A cls entry above 15 is BPE_GPU_EINVAL. */
 int bpe_gpu_split(bpe_gpu_ctx *ctx, const uint8_t *cls, const uint16_t *brk, size_t *ndocs);
-/* the same by a preset: BPE_SPLIT_LINES / BPE_SPLIT_WORDS are bpe_gpu_split with their tables, BPE_SPLIT_GPT2 and
-   BPE_SPLIT_GPT2_UNICODE mark the starts with kernels of their own; the offsets and all that is said of them above are the same.
+/* the same by a preset: BPE_SPLIT_LINES / BPE_SPLIT_WORDS are bpe_gpu_split with their tables, BPE_SPLIT_GPT2,
+   BPE_SPLIT_GPT2_UNICODE and BPE_SPLIT_CL100K mark the starts with kernels of their own; the offsets and all that is said of them above are the same.
    BPE_GPU_EINVAL for another preset, BPE_GPU_ESTATE before a load. */
 int bpe_gpu_split_preset(bpe_gpu_ctx *ctx, int preset, size_t *ndocs);
 /* the last split's offsets; out may be NULL, *count = ndocs + 1 */
@@ -420,7 +456,11 @@ int bpe_gpu_fetch_piece_table(bpe_gpu_ctx *ctx, uint64_t *start, uint32_t *len, 
  * the bytes at and past n do.  Only positions s - 1 and e .. e + 3 can differ
  * from the marks without specials.  BPE_SPLIT_GPT2_UNICODE reads the bytes near
  * a match the same way, before decoding (a sequence a match cuts is ill-formed);
- * there positions s - 7 .. s - 1 and e .. e + 6 can differ.  With S == 0 the offsets are those of
+ * there positions s - 7 .. s - 1 and e .. e + 6 can differ.  BPE_SPLIT_CL100K
+ * reads them the same way again; a match thereby ends every run: the numbers
+ * after it count from it, the newlines after it follow no P, and white space
+ * before it has no newline beyond it.  No fixed set of positions bounds what can
+ * differ there, so its marking pass reads the matches itself.  With S == 0 the offsets are those of
  * bpe_gpu_split / bpe_gpu_split_preset.
  *
  * Ids.  Special j (the caller's list order) has the id 256 + n_merges + j for

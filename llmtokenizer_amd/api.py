@@ -172,13 +172,13 @@ def encode_batch(docs, merges, device=0):
     return _take_ids(p, n.value), offsets
 
 
-# bpe_gpu.h BPE_SPLIT_LINES / BPE_SPLIT_WORDS / BPE_SPLIT_GPT2 / BPE_SPLIT_GPT2_UNICODE (3 is no preset)
-SPLIT_PRESETS = {"lines": 0, "words": 1, "gpt2": 2, "gpt2_unicode": 4}
+# bpe_gpu.h BPE_SPLIT_LINES / BPE_SPLIT_WORDS / BPE_SPLIT_GPT2 / BPE_SPLIT_GPT2_UNICODE / BPE_SPLIT_CL100K (3 and 5 are no presets)
+SPLIT_PRESETS = {"lines": 0, "words": 1, "gpt2": 2, "gpt2_unicode": 4, "cl100k": 6}
 TABLE_PRESETS = ("lines", "words")  # the presets two tables express
 
 
 def _no_tables(rule):
-    """is rule the name of a preset without tables ("gpt2", "gpt2_unicode": the preset calls run them)?"""
+    """is rule the name of a preset without tables ("gpt2", "gpt2_unicode", "cl100k": the preset calls run them)?"""
     return isinstance(rule, str) and rule in SPLIT_PRESETS and rule not in TABLE_PRESETS
 
 
@@ -203,7 +203,7 @@ def split_rule(preset):
     """The tables (cls uint8[256], brk uint16[16]) of a preset split rule, "lines"
     or "words" (bpe_gpu.h bpe_gpu_split_rule; this project's rules, not GPT-2's
     regular expression): a piece starts at byte i when bit cls[b[i]] of
-    brk[cls[b[i - 1]]] is set, and at byte 0.  "gpt2" and "gpt2_unicode" have no
+    brk[cls[b[i - 1]]] is set, and at byte 0.  "gpt2", "gpt2_unicode" and "cl100k" have no
     tables (a start there depends on six and fifteen bytes): pass the name to
     split / encode_split / train_split / split_host."""
     if _no_tables(preset):
@@ -274,7 +274,7 @@ def split_host_special(data: bytes, rule, specials):
 
 def split_host(data: bytes, rule, specials=None):
     """The offsets (uint64: the piece starts followed by len(data)) of a preset
-    rule, "lines", "words", "gpt2" or "gpt2_unicode", computed on the host in plain C
+    rule, "lines", "words", "gpt2", "gpt2_unicode" or "cl100k", computed on the host in plain C
     (bpe_ex.h bpe_split_offsets_host): the definition Engine.split(rule) is held
     to.  With specials (a list of bytes-like objects, see check_specials) the
     definition of Engine.split(rule, specials), for a preset or a (cls, brk)
@@ -314,7 +314,8 @@ def _rule_tables(rule):
 
 def encode_split(data: bytes, merges, rule="words", device=0, specials=None):
     """Split data into pieces on the GPU (rule: a preset name, "lines", "words",
-    "gpt2" or "gpt2_unicode", or a (cls, brk) pair, see split_rule) and encode the pieces as documents.  Returns (ids,
+    "gpt2", "gpt2_unicode" or "cl100k" (the pre-tokenizer of cl100k_base and Llama 3), or a (cls, brk) pair, see
+    split_rule) and encode the pieces as documents.  Returns (ids,
     id_offsets, byte_offsets), both offsets uint64 of length pieces + 1: piece d
     is data[byte_offsets[d]:byte_offsets[d + 1]] and its ids are
     ids[id_offsets[d]:id_offsets[d + 1]] == encode(piece d, merges).  With specials (a list of
@@ -515,7 +516,7 @@ class Engine:
 
     def split(self, rule="words", specials=None):
         """split the resident bytes into pieces on the device (rule: a preset
-        name, "lines", "words", "gpt2" or "gpt2_unicode", or a (cls, brk) pair, see split_rule); the offsets stay in HBM for
+        name, "lines", "words", "gpt2", "gpt2_unicode" or "cl100k", or a (cls, brk) pair, see split_rule); the offsets stay in HBM for
         encode_split().  With specials (a list of bytes-like objects, see check_specials) every occurrence of
         one is a piece of its own (bpe_gpu_split_special); they last as long as the offsets, and a split
         without them forgets them.  Returns the number of pieces."""

@@ -357,9 +357,10 @@ struct bpe_gpu_ctx {
     // temporaries 26, tokens and their entries 27-30, rewrite flags and scans 31-34, pair table 35-37),
     // of the special tokens (the set 38, cover bitmap 39, match list and its sorted copy 40-41, sort and scan
     // temporaries 42, control words 43, the post-pass's first ids / removed ids / their scan 44-46, the
-    // decoder's bytes and offsets 47-48), and the pinned staging of file loads
-    void *dscr[49] = {};
-    size_t dscr_cap[49] = {};
+    // decoder's bytes and offsets 47-48), of BPE_SPLIT_CL100K (the chain effects and their scan 49, the scan's
+    // temporary 50), and the pinned staging of file loads
+    void *dscr[51] = {};
+    size_t dscr_cap[51] = {};
     std::vector<uint32_t> ew_stage;  // host image of the window encoder's tables (outlives the upload)
     uint8_t *stage[2] = {};
     hipEvent_t stage_ev[2] = {};
@@ -3476,6 +3477,7 @@ int bpe_gpu_split_rule(int preset, uint8_t *cls, uint16_t *brk) {
     if (preset == BPE_SPLIT_GPT2) return fail(BPE_GPU_EINVAL, "split_rule: BPE_SPLIT_GPT2 has no tables (bpe_gpu_split_preset)");
     if (preset == BPE_SPLIT_GPT2_UNICODE)
         return fail(BPE_GPU_EINVAL, "split_rule: BPE_SPLIT_GPT2_UNICODE has no tables (bpe_gpu_split_preset)");
+    if (preset == BPE_SPLIT_CL100K) return fail(BPE_GPU_EINVAL, "split_rule: BPE_SPLIT_CL100K has no tables (bpe_gpu_split_preset)");
     if (preset != BPE_SPLIT_WORDS) return fail(BPE_GPU_EINVAL, "split_rule: no such preset");
     for (int b = 0; b < 256; b++)
         cls[b] = (b >= 'A' && b <= 'Z') || (b >= 'a' && b <= 'z') || b >= 0x80 ? 1
@@ -3501,12 +3503,13 @@ static uint32_t sx_grid(uint64_t items) {
     return (uint32_t)std::min<uint64_t>(std::max<uint64_t>((items + SX_T - 1) / SX_T, 1), SX_GRID);
 }
 
-// The special passes of a split, between the marking kernel and the count scan (special.hip): find, and when
-// there are matches patch, recount and sort.  *M matches, *sorted their list by start (scratch slot 41).
-static int sp_mark(bpe_gpu_ctx *c, const SpSet *sp, int gpt2, uint64_t n, uint64_t ntiles, uint32_t grid, uint16_t *mask,
-                   uint32_t *wcnt, uint32_t *M, unsigned long long **sorted, uint64_t *info) {
+// The special passes of a split (special.hip).  sp_find: the matches, *M of them, their list in scratch slot 40
+// and the cover bitmap in slot 39; it runs after the marking kernel, or before it for BPE_SPLIT_CL100K, whose
+// marking kernel reads the bitmap.  sp_patch, between the marking kernel and the count scan when there are
+// matches: patch, recount and sort; *sorted the list by start (scratch slot 41).
+static int sp_find(bpe_gpu_ctx *c, const SpSet *sp, uint64_t n, uint64_t ntiles, uint32_t grid, uint32_t *M, uint64_t *info) {
     int r;
-    void *pset, *pcov, *pctl, *plist = nullptr, *psort, *tmp;
+    void *pset, *pcov, *pctl, *plist = nullptr;
     const size_t cov_bytes = ntiles * SP_T * 2;  // a bit per byte of the whole tiles
     if ((r = dscratch(c, 38, sizeof(SpSet), &pset)) || (r = dscratch(c, 39, cov_bytes, &pcov)) || (r = dscratch(c, 43, 64, &pctl)))
         return r;
@@ -3532,6 +3535,13 @@ static int sp_mark(bpe_gpu_ctx *c, const SpSet *sp, int gpt2, uint64_t n, uint64
     info[1] = found;
     info[3] = cap;
     *M = found;
+    return 0;
+}
+
+static int sp_patch(bpe_gpu_ctx *c, int gpt2, uint64_t n, uint64_t ntiles, uint32_t grid, uint16_t *mask, uint32_t *wcnt,
+                    uint32_t found, unsigned long long **sorted) {
+    int r;
+    void *pset = c->dscr[38], *pcov = c->dscr[39], *plist = c->dscr[40], *psort, *tmp;
     *sorted = nullptr;
     if (!found) return 0;
     k_sp_patch<<<sx_grid(found), SX_T, 0, c->st>>>(c->h.bytes, n, (const unsigned long long *)plist, found, (const SpSet *)pset,
@@ -3549,8 +3559,9 @@ static int sp_mark(bpe_gpu_ctx *c, const SpSet *sp, int gpt2, uint64_t n, uint64
 }
 
 // the body of bpe_gpu_split (R: the tables) and of bpe_gpu_split_preset's BPE_SPLIT_GPT2 and BPE_SPLIT_GPT2_UNICODE
-// (R == nullptr; gpt2: 1 the first, 2 the second; sp_mark hands it to k_sp_patch): all but
-// the marking launch is one code, so the offsets and their lifetime are the same whichever kernel marked the starts.
+// and BPE_SPLIT_CL100K (R == nullptr; gpt2: 1 the first, 2 the second, 3 the third; sp_patch hands 1 and 2 to
+// k_sp_patch; 3 has read the matches while marking): all but the marking launches is one code, so the offsets and
+// their lifetime are the same whichever kernel marked the starts.
 // sp: the specials of bpe_gpu_split_special (nullptr: none, and nothing but the launches below runs)
 static int split_run(bpe_gpu_ctx *c, const SplitRule *R, size_t *ndocs, const SpSet *sp = nullptr, int gpt2 = 0) {
     if (!R && !gpt2) gpt2 = 1;
@@ -3578,17 +3589,35 @@ static int split_run(bpe_gpu_ctx *c, const SplitRule *R, size_t *ndocs, const Sp
         uint32_t *wcnt = (uint32_t *)(woff + nwt + 1);
         const uint32_t grid = (uint32_t)std::min<uint64_t>(ntiles, SP_GRID);
         HIPCHK(hipMemsetAsync(wcnt + nwt, 0, 4, c->st));
+        if (sp && gpt2 == 3 && (r = sp_find(c, sp, n, ntiles, grid, &sp_M, sp_info))) return r;
         if (R) {
             k_split_table<<<SP_TBL / SP_T, SP_T, 0, c->st>>>(*R, (uint32_t *)tbl);
             HIPCHK(hipGetLastError());
             k_split_mark<<<grid, SP_T, 0, c->st>>>(c->h.bytes, n, (const uint32_t *)tbl, ntiles, mask, wcnt);
+        } else if (gpt2 == 3) {
+            // the effects of the wave tiles on the three chains, their scan, and the marks (split.hip).  One scan
+            // serves both directions: sum_f[nwt], a reset (the summary kernel writes it), sum_b[nwt] (the tiles in
+            // reverse order)
+            void *pcl, *ptmp;
+            const size_t cnt = 2 * nwt + 1;
+            if ((r = dscratch(c, 49, 2 * cnt * 4, &pcl))) return r;
+            uint32_t *sum = (uint32_t *)pcl, *in = sum + cnt;
+            const uint32_t *cover = sp ? (const uint32_t *)c->dscr[39] : nullptr;
+            k_cl_summary<<<grid, SP_T, 0, c->st>>>(c->h.bytes, n, ntiles, cover, sum, sum + nwt + 1);
+            HIPCHK(hipGetLastError());
+            size_t tb = 0;
+            HIPCHK(rocprim::exclusive_scan(nullptr, tb, sum, in, CL_RESET, cnt, ClCompose(), c->st));
+            if ((r = dscratch(c, 50, tb, &ptmp))) return r;
+            HIPCHK(rocprim::exclusive_scan(ptmp, tb, sum, in, CL_RESET, cnt, ClCompose(), c->st));
+            k_split_mark_cl100k<<<grid, SP_T, 0, c->st>>>(c->h.bytes, n, ntiles, cover, in, in + nwt + 1, mask, wcnt);
         } else if (gpt2 == 2) {
             k_split_mark_gpt2u<<<grid, SP_T, 0, c->st>>>(c->h.bytes, n, ntiles, mask, wcnt);
         } else {
             k_split_mark_gpt2<<<grid, SP_T, 0, c->st>>>(c->h.bytes, n, ntiles, mask, wcnt);
         }
         HIPCHK(hipGetLastError());
-        if (sp && (r = sp_mark(c, sp, R ? 0 : gpt2, n, ntiles, grid, mask, wcnt, &sp_M, &sp_sorted, sp_info))) return r;
+        if (sp && gpt2 != 3 && (r = sp_find(c, sp, n, ntiles, grid, &sp_M, sp_info))) return r;
+        if (sp && (r = sp_patch(c, R || gpt2 == 3 ? 0 : gpt2, n, ntiles, grid, mask, wcnt, sp_M, &sp_sorted))) return r;
         size_t tb = 0;
         HIPCHK(rocprim::exclusive_scan(nullptr, tb, wcnt, woff, 0ull, nwt + 1, rocprim::plus<unsigned long long>(), c->st));
         if ((r = dscratch(c, 15, tb, &tmp))) return r;
@@ -3659,11 +3688,12 @@ int bpe_gpu_split(bpe_gpu_ctx *c, const uint8_t *cls, const uint16_t *brk, size_
 
 int bpe_gpu_split_preset(bpe_gpu_ctx *c, int preset, size_t *ndocs) {
     if (!c || !ndocs) return BPE_GPU_EINVAL;
-    if (preset != BPE_SPLIT_LINES && preset != BPE_SPLIT_WORDS && preset != BPE_SPLIT_GPT2 && preset != BPE_SPLIT_GPT2_UNICODE)
+    if (preset != BPE_SPLIT_LINES && preset != BPE_SPLIT_WORDS && preset != BPE_SPLIT_GPT2 && preset != BPE_SPLIT_GPT2_UNICODE &&
+        preset != BPE_SPLIT_CL100K)
         return fail(BPE_GPU_EINVAL, "split_preset: no such preset");
-    if (preset == BPE_SPLIT_GPT2 || preset == BPE_SPLIT_GPT2_UNICODE) {
+    if (preset == BPE_SPLIT_GPT2 || preset == BPE_SPLIT_GPT2_UNICODE || preset == BPE_SPLIT_CL100K) {
         if (!c->loaded) return fail(BPE_GPU_ESTATE, "split before load");
-        return split_run(c, nullptr, ndocs, nullptr, preset == BPE_SPLIT_GPT2 ? 1 : 2);
+        return split_run(c, nullptr, ndocs, nullptr, preset == BPE_SPLIT_GPT2 ? 1 : preset == BPE_SPLIT_GPT2_UNICODE ? 2 : 3);
     }
     uint8_t cls[256];
     uint16_t brk[16];
@@ -3676,7 +3706,7 @@ int bpe_gpu_split_special(bpe_gpu_ctx *c, int preset, const uint8_t *cls, const 
     if (!c || !ndocs) return BPE_GPU_EINVAL;
     if (preset < 0 && (!cls || !brk)) return fail(BPE_GPU_EINVAL, "split_special: no preset and no tables");
     if (preset >= 0 && preset != BPE_SPLIT_LINES && preset != BPE_SPLIT_WORDS && preset != BPE_SPLIT_GPT2 &&
-        preset != BPE_SPLIT_GPT2_UNICODE)
+        preset != BPE_SPLIT_GPT2_UNICODE && preset != BPE_SPLIT_CL100K)
         return fail(BPE_GPU_EINVAL, "split_special: no such preset");
     char msg[400];
     if (bpe_specials_check(specials, msg, sizeof msg)) return fail(BPE_GPU_EINVAL, msg);
@@ -3709,6 +3739,7 @@ int bpe_gpu_split_special(bpe_gpu_ctx *c, int preset, const uint8_t *cls, const 
     SplitRule R;
     if (preset == BPE_SPLIT_GPT2) return split_run(c, nullptr, ndocs, &H, 1);
     if (preset == BPE_SPLIT_GPT2_UNICODE) return split_run(c, nullptr, ndocs, &H, 2);
+    if (preset == BPE_SPLIT_CL100K) return split_run(c, nullptr, ndocs, &H, 3);
     if (preset >= 0) {
         uint8_t pc[256];
         const int r = bpe_gpu_split_rule(preset, pc, R.brk);

@@ -19,6 +19,8 @@
 //                 and e + 1 .. e + 6 and the rule is split.hip's su_starts over b[i - 7 .. i + 7].  Two matches may touch one mask word and may decide the same
 //                 position: every write is an atomicOr or atomicAnd of bits whose value is a function
 //                 of the bytes and the (complete) cover bitmap alone, so the order does not matter.
+//                 For BPE_SPLIT_CL100K nothing is decided again: k_sp_find runs before that rule's marking
+//                 kernels, which read the cover bitmap themselves (split.hip), and the patch sets s and e alone.
 //   k_sp_recount  the per-1,024-byte counts again from the masks: the scan and k_split_emit run as they are.
 //   (rocprim::radix_sort_keys of the match list by start)
 //   k_sp_pieces   start -> piece index, a binary search of the emitted offsets; the list stays resident.

@@ -122,7 +122,7 @@ int bpe_split_offsets_host_special(int preset, const uint8_t *cls, const uint16_
         for (int b = 0; b < 256; b++)
             if (cls[b] > 15) return BPE_GPU_EINVAL;
     } else if (preset != BPE_SPLIT_LINES && preset != BPE_SPLIT_WORDS && preset != BPE_SPLIT_GPT2 &&
-               preset != BPE_SPLIT_GPT2_UNICODE) {
+               preset != BPE_SPLIT_GPT2_UNICODE && preset != BPE_SPLIT_CL100K) {
         return BPE_GPU_EINVAL;
     }
     int rc = bpe_specials_check(sp, NULL, 0);

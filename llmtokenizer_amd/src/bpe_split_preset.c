@@ -1,7 +1,7 @@
 /*
  * bpe_split_preset.c -- the preset split rules of bpe_ex.h: the rules in plain C
  * (bpe_split_offsets_host: the written definition the device kernels are held
- * to, no GPU), and bpe_encode_split_preset / bpe_train_split_preset over
+ * to, no GPU; BPE_SPLIT_CL100K among them), and bpe_encode_split_preset / bpe_train_split_preset over
  * bpe_gpu_split_preset, on the bodies bpe_encode_split and bpe_train_split run.
  */
 #include "bpe_internal.h"
@@ -143,6 +143,99 @@ static int starts_gpt2u(const uint8_t *b, size_t n, size_t i)
     return c != p;
 }
 
+/* ---- BPE_SPLIT_CL100K: the rule of bpe_gpu.h, one pass from the left over the characters of the text */
+
+enum { C_R = 5 }; /* \r and \n, split off from C_W for this rule */
+
+/* the character that begins at byte i < n (i is no byte inside a well-formed sequence): its class with R,
+ * *end the offset just past it, *fold the letter a contraction reads there (A-Z folded, U+017F an s) or 0 */
+static int cl_char(const uint8_t *b, size_t n, size_t i, size_t *end, int *fold)
+{
+    uint32_t cp = 0;
+    const int len = u8_seq(b, n, i, &cp);
+    *end = i + (len ? (size_t)len : 1);
+    *fold = 0;
+    if (!len) return C_P; /* a byte in no well-formed sequence */
+    if (cp == '\r' || cp == '\n') return C_R;
+    if (cp >= 'A' && cp <= 'Z') *fold = (int)cp + ('a' - 'A');
+    else if (cp >= 'a' && cp <= 'z') *fold = (int)cp;
+    else if (cp == 0x17F) *fold = 's';
+    return bpe_unicode_class(cp);
+}
+
+/* the characters (2 or 3) of the contraction whose apostrophe is at byte j, or 0; the class before it is the caller's */
+static int cl_clen(const uint8_t *b, size_t n, size_t j)
+{
+    size_t e1, e2;
+    int x = 0, y = 0;
+    if (j + 1 >= n) return 0;
+    (void)cl_char(b, n, j + 1, &e1, &x);
+    if (x == 's' || x == 't' || x == 'm' || x == 'd') return 2;
+    if (e1 >= n) return 0;
+    (void)cl_char(b, n, e1, &e2, &y);
+    return ((x == 'r' || x == 'v') && y == 'e') || (x == 'l' && y == 'l') ? 3 : 0;
+}
+
+static int is_ws(int c) { return c == C_S || c == C_W || c == C_R; }
+
+/* the starts of text b[0 .. n) under BPE_SPLIT_CL100K, in order: out[k] written below cap, *k their number */
+static void starts_cl100k(const uint8_t *b, size_t n, uint64_t *out, size_t cap, size_t *k)
+{
+    int p = C_R, pp = C_R;  /* the classes of the two characters before this one: before the text all reads as R */
+    size_t nrun = 0;        /* numbers in the run that ends just before this character, mod 3 */
+    int armed = 0;          /* every character since the last P is R (chain A) */
+    int inside = 0;         /* characters of a contraction still to come */
+    int after = 0;          /* the character before this one ended a contraction */
+    size_t q = 0, last_r = 0; /* the white-space run this character is in ends at byte q; has_r: its last R is at byte last_r */
+    int has_r = 0;
+    size_t end;
+    for (size_t i = 0; i < n; i = end) {
+        int fold;
+        const int c = cl_char(b, n, i, &end, &fold);
+        int s;
+        if (is_ws(c) && (i == 0 || !is_ws(p))) { /* a run begins: look ahead through it once */
+            has_r = 0;
+            for (q = i; q < n;) {
+                size_t e;
+                int f;
+                const int x = cl_char(b, n, q, &e, &f);
+                if (!is_ws(x)) break;
+                if (x == C_R) has_r = 1, last_r = q;
+                q = e;
+            }
+        }
+        if (c == C_N) {
+            s = nrun == 0; /* (0 after a character that is no number) */
+        } else if (is_ws(c)) {
+            if (!is_ws(p)) s = !(p == C_P && c == C_R);
+            else if (c == C_R) s = 0;
+            else s = (end == q && q < n) || (p == C_R && !(has_r && last_r >= i)) || (p == C_R && armed);
+        } else if (c == C_L) {
+            if (inside) s = 0;
+            else if (after) s = 1;
+            else if (p == C_L) s = 0;
+            else if (p == C_N || p == C_R) s = 1;
+            else if (p == C_S || p == C_W) s = 0;
+            else s = pp == C_P || pp == C_S;
+        } else {
+            s = p == C_L || p == C_N || p == C_R || p == C_W;
+        }
+        if (i == 0) s = 1;
+        if (s) {
+            if (out && *k < cap) out[*k] = i;
+            ++*k;
+        }
+        /* the state the next character reads */
+        after = 0;
+        if (inside) after = --inside == 0;
+        else if (c == C_P && b[i] == '\'' && p != C_P && p != C_S) inside = cl_clen(b, n, i) ? cl_clen(b, n, i) - 1 : 0;
+        nrun = c == C_N ? (nrun + 1) % 3 : 0;
+        armed = c == C_P ? 1 : c == C_R ? armed : 0;
+        pp = p;
+        p = c;
+    }
+}
+
 static int starts_words(const uint8_t *b, size_t i)
 {
     const int c = class_of(b[i]), p = class_of(b[i - 1]);
@@ -152,9 +245,16 @@ static int starts_words(const uint8_t *b, size_t i)
 int bpe_split_offsets_host(int preset, const uint8_t *bytes, size_t n, uint64_t *out, size_t cap, size_t *count)
 {
     if ((!bytes && n) || !count) return BPE_GPU_EINVAL;
-    if (preset != BPE_SPLIT_LINES && preset != BPE_SPLIT_WORDS && preset != BPE_SPLIT_GPT2 && preset != BPE_SPLIT_GPT2_UNICODE)
+    if (preset != BPE_SPLIT_LINES && preset != BPE_SPLIT_WORDS && preset != BPE_SPLIT_GPT2 && preset != BPE_SPLIT_GPT2_UNICODE &&
+        preset != BPE_SPLIT_CL100K)
         return BPE_GPU_EINVAL;
     size_t k = 0;
+    if (preset == BPE_SPLIT_CL100K) {
+        starts_cl100k(bytes, n, out, cap, &k);
+        if (out && k < cap) out[k] = n;
+        *count = k + 1;
+        return 0;
+    }
     for (size_t i = 0; i < n; i++) {
         const int s = i == 0                     ? 1
                       : preset == BPE_SPLIT_GPT2_UNICODE ? starts_gpt2u(bytes, n, i)

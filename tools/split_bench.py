@@ -5,17 +5,22 @@ encode_split against the host-offset path it replaces.
 Two 1 GiB corpora resident in HBM: the seed-3 synthetic corpus (Engine.synth;
 printable bytes, no newline) and english_like (a 32 MiB sample generated on the
 host and repeated to the size).  Three rules: the table rules "lines" and
-"words", and "gpt2" and "gpt2_unicode" (bpe_gpu_split_preset; their own marking
-kernels).  A third corpus, english_nonascii, is english_like with every
+"words", and "gpt2", "gpt2_unicode" and "cl100k" (bpe_gpu_split_preset; their own
+marking kernels).  A third corpus, english_nonascii, is english_like with every
 --nonascii-th letter replaced by a two-byte Cyrillic letter (D0 B0..BF): the
 ASCII corpora take gpt2_unicode's all-ASCII path, this one its decoding path.
+Two more are one run each, for the rules whose starts depend on the position in
+a run ("cl100k"): digits (the ten digits over and over) and spaces_newline
+(spaces and one final newline).  --corpora selects among the five.
 
   split    Engine.split(rule) alone, alternated with a device-to-device
            hipMemcpyAsync of the same number of bytes timed the same way (host
            clock around launch + stream synchronise): the streaming yardstick
            of the box.  Reported: ms, pieces, the bytes the design moves
            (n read, n / 8 of start masks written and read again, 8 B per offset
-           written, 12 B per 1,024 bytes of counts and their scan) per second,
+           written, 12 B per 1,024 bytes of counts and their scan; for "cl100k" n
+           read once more by its summary pass and 16 B per 1,024 bytes of chain
+           effects and their scan) per second,
            and that rate over the copy's (2 n bytes per copy).
   split_ab per corpus, Engine.split("words") and Engine.split("gpt2") alternated in
            one loop: the two marking kernels side by side (their emit passes
@@ -75,7 +80,8 @@ def nonascii(sample, every):
     return out
 
 
-NO_TABLES = ("gpt2", "gpt2_unicode")
+NO_TABLES = ("gpt2", "gpt2_unicode", "cl100k")
+CORPORA = ("seed3", "english_like", "english_nonascii", "digits", "spaces_newline")
 
 
 def med(xs):
@@ -134,7 +140,8 @@ def main():
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--sample", type=int, default=1 << 25, help="bytes of english_like generated, then repeated")
     ap.add_argument("--no-e2e", action="store_true", help="the split alone")
-    ap.add_argument("--rules", default="lines,words,gpt2,gpt2_unicode", help="the rules to run, comma separated")
+    ap.add_argument("--rules", default="lines,words,gpt2,gpt2_unicode,cl100k", help="the rules to run, comma separated")
+    ap.add_argument("--corpora", default=",".join(CORPORA), help="the corpora to run, comma separated")
     ap.add_argument("--nonascii", type=int, default=4, help="english_nonascii: one letter in this many is two bytes")
     ap.add_argument("--check-bytes", type=int, default=0,
                     help="with --no-e2e: compare the device's offsets with split_host over this many leading bytes")
@@ -156,10 +163,17 @@ def main():
     cp = DeviceCopy(n)
     e = api.Engine(args.device)
     sample = np.frombuffer(english_like(min(args.sample, n)), np.uint8)
-    for corpus in ("seed3", "english_like", "english_nonascii"):
+    for corpus in args.corpora.split(","):
+        if corpus not in CORPORA:
+            sys.exit(f"split_bench: no corpus {corpus!r} (have {CORPORA})")
         if corpus == "seed3":
             e.synth(3, n)
             host = None
+        elif corpus in ("digits", "spaces_newline"):  # one run as long as the text
+            host = np.tile(np.frombuffer(b"0123456789", np.uint8), n // 10 + 1)[:n] if corpus == "digits" else np.full(n, 0x20, np.uint8)
+            if corpus == "spaces_newline":
+                host[-1] = 0x0A
+            e.load(host.tobytes())
         else:
             part = sample if corpus == "english_like" else nonascii(sample, args.nonascii)
             host = np.tile(part, (n + part.size - 1) // part.size)[:n]
@@ -175,7 +189,7 @@ def main():
                 t1 = time.perf_counter()
                 t_split.append(t1 - t0)
                 t_copy.append(cp.run())
-            moved = n + n // 4 + 8 * (nd + 1) + 12 * (n // 1024)
+            moved = n + n // 4 + 8 * (nd + 1) + 12 * (n // 1024) + (n + 16 * (n // 1024) if rule == "cl100k" else 0)
             ms, mc = med(t_split), med(t_copy)
             rate = moved / (ms["ms_median"] * 1e-3) / 1e9
             copy_rate = 2 * n / (mc["ms_median"] * 1e-3) / 1e9
@@ -190,7 +204,7 @@ def main():
                     want = api.split_host(head, rule)[:-16]  # (the last pieces of the head see its end)
                     if not (e.split_offsets()[:want.size] == want).all():
                         sys.exit(f"split_bench: {key}: the device's offsets differ from split_host")
-                    out["split"][key]["offsets_equal_split_host_over_bytes"] = int(want[-1])
+                    out["split"][key]["offsets_equal_split_host_over_bytes"] = int(want[-1]) if want.size else 0
                 continue
             if host is None:  # the parent path's user holds the text on the host
                 host = np.frombuffer(synth_bytes(3, n), np.uint8)
@@ -235,7 +249,7 @@ def main():
                 "single_spread": round((s["ms_max"] - s["ms_min"]) / s["ms_median"], 4)}
             del off
             print(json.dumps({"progress": key, **out["e2e"][key]}), file=sys.stderr, flush=True)
-        ab = {rule: [] for rule in ("words", "gpt2", "gpt2_unicode") if rule in args.rules.split(",")}
+        ab = {rule: [] for rule in ("words", "gpt2", "gpt2_unicode", "cl100k") if rule in args.rules.split(",")}
         for _ in range(reps):
             for rule, ts in ab.items():
                 t0 = time.perf_counter()
