@@ -30,7 +30,7 @@ COBJ_SP := $(patsubst $(PKG)/src/%.c,$(BUILD)/%.o,$(CSRC_SP))
 CSRC_SPECIAL := $(PKG)/src/bpe_special.c
 CSRC_SPECIAL_GPU := $(PKG)/src/bpe_special_gpu.c
 COBJ_SPECIAL := $(patsubst $(PKG)/src/%.c,$(BUILD)/%.o,$(CSRC_SPECIAL) $(CSRC_SPECIAL_GPU))
-HIPDEPS := $(wildcard $(PKG)/csrc/*.hip $(PKG)/csrc/*.h) include/bpe_gpu.h
+HIPDEPS := $(wildcard $(PKG)/csrc/*.hip $(PKG)/csrc/*.h) $(PKG)/src/bpe_split_presets.h include/bpe_gpu.h
 
 all: $(PKG)/libbpe_amd.so tools/bpe_main oracle
 

@@ -316,7 +316,8 @@ struct bpe_gpu_ctx {
     size_t sp_cap = 0;  // entries d_sp_pieces holds
     uint64_t sp_info[4] = {};
     // the last bpe_gpu_train_split over those offsets: its merges (host), bpe_gpu_train_split_info's fields and
-    // the piece table (scratch slots 22-24).  Valid while split_ready: whatever drops the offsets drops these.
+    // the piece table (scratch slots DS_TS_ESTART, DS_TS_ELEN, DS_TS_ECNT).  Valid while split_ready: whatever drops
+    // the offsets drops these.
     bool ts_ready = false;
     std::vector<uint32_t> ts_merges;
     uint64_t ts_info[8] = {};
@@ -349,18 +350,9 @@ struct bpe_gpu_ctx {
     hipEvent_t cp_ev[2] = {};
     bool cp_pending = false;
     uint64_t prof_launches = 0;
-    // grow-only device scratch of decode (ids, pairs, elen, offsets, scan
-    // temporaries, output, error words; slots 0-6), of the window encoder
-    // (tables, halo bytes, rank exchange; 7-9), of bpe_gpu_decode_docs (id and byte offsets; 10-11),
-    // of bpe_gpu_split (start table, start masks, wave counts + their scan, scan temporaries; 12-15),
-    // of bpe_gpu_train_split (piece table 16-17, control words 18, entry records 19-25, scan and sort
-    // temporaries 26, tokens and their entries 27-30, rewrite flags and scans 31-34, pair table 35-37),
-    // of the special tokens (the set 38, cover bitmap 39, match list and its sorted copy 40-41, sort and scan
-    // temporaries 42, control words 43, the post-pass's first ids / removed ids / their scan 44-46, the
-    // decoder's bytes and offsets 47-48), of BPE_SPLIT_CL100K (the chain effects and their scan 49, the scan's
-    // temporary 50), and the pinned staging of file loads
-    void *dscr[51] = {};
-    size_t dscr_cap[51] = {};
+    // grow-only device scratch (DScr, engine_common.h) and the pinned staging of file loads
+    void *dscr[DS_COUNT] = {};
+    size_t dscr_cap[DS_COUNT] = {};
     std::vector<uint32_t> ew_stage;  // host image of the window encoder's tables (outlives the upload)
     uint8_t *stage[2] = {};
     hipEvent_t stage_ev[2] = {};
@@ -1404,7 +1396,7 @@ struct Resolver {
 // stops (Eng::hprobe); a replay queued behind a stop finds the stop set and
 // every kernel in it exits at once.  Returns with the stream still busy (the
 // caller's pull_ctl synchronises).  Nothing is queued past the merge cap.
-int dscratch(bpe_gpu_ctx *c, int k, size_t bytes, void **out);
+int dscratch(bpe_gpu_ctx *c, DScr k, size_t bytes, void **out);
 
 // Rebuild the byte-pair position lists from the live tokens (k_relist_hist,
 // the init sort's column scans, k_relist_scatter); the stream is idle here
@@ -1419,7 +1411,7 @@ int relist(bpe_gpu_ctx *c) {
     const uint32_t ngr = (ntl + per - 1) / per;
     void *p;
     int r;
-    if ((r = dscratch(c, 9, ((size_t)ntl * AA + (size_t)ngr * AA + AA + 1) * 4, &p))) return r;
+    if ((r = dscratch(c, DS_EW_XCHG, ((size_t)ntl * AA + (size_t)ngr * AA + AA + 1) * 4, &p))) return r;
     uint32_t *d_hist = (uint32_t *)p, *d_gsum = d_hist + (size_t)ntl * AA, *d_tot = d_gsum + (size_t)ngr * AA;
     k_relist_hist<<<ntl, RELIST_T, AA * 4, c->st>>>(c->dE, d_hist, tile);
     const dim3 cgrid((AA + 255) / 256, ngr);
@@ -2056,7 +2048,7 @@ void fill_profile(bpe_gpu_ctx *c) {
 }
 
 // grow-only device scratch slot k of at least `bytes`
-int dscratch(bpe_gpu_ctx *c, int k, size_t bytes, void **out) {
+int dscratch(bpe_gpu_ctx *c, DScr k, size_t bytes, void **out) {
     if (bytes > c->dscr_cap[k]) {
         if (c->dscr[k]) {
             HIPCHK(hipStreamSynchronize(c->st));
@@ -2071,6 +2063,27 @@ int dscratch(bpe_gpu_ctx *c, int k, size_t bytes, void **out) {
     *out = c->dscr[k];
     return 0;
 }
+template <class T>
+int dscratch(bpe_gpu_ctx *c, DScr k, size_t bytes, T **out) {  // ... as an array of T
+    void *p = nullptr;
+    const int r = dscratch(c, k, bytes, &p);
+    *out = (T *)p;
+    return r;
+}
+
+// rocprim's two calls: ask for the temporary's size, take scratch slot k for it, run.  run(tmp, bytes) is the call and
+// what its text, the message of a failure.  ROCPRIM_RUN(c, k, rocprim::f(tmp, tb, ...)) writes both.
+template <class F>
+int rocprim_run(bpe_gpu_ctx *c, DScr k, const char *what, F run) {
+    size_t tb = 0;
+    void *tmp = nullptr;
+    hipError_t e = run(tmp, tb);
+    const int r = e == hipSuccess ? dscratch(c, k, tb, &tmp) : 0;
+    if (r) return r;
+    if (e == hipSuccess) e = run(tmp, tb);
+    return e == hipSuccess ? 0 : fail(BPE_GPU_EHIP, what, e);
+}
+#define ROCPRIM_RUN(c, k, call) rocprim_run(c, k, #call, [&](void *tmp, size_t &tb) { return call; })
 
 // a context on `device`; shared == nullptr creates its own stream
 int ctx_new(int device, hipStream_t shared, bpe_gpu_ctx **out) {
@@ -2340,11 +2353,8 @@ int ew_run(bpe_gpu_ctx *c, const EwPlan &P, const uint32_t *d_img, uint32_t halo
     if (nwin) k_enc_win<<<grid, EW_T, 0, c->st>>>(A);
     HIPCHK(hipGetLastError());
     // window offsets (exclusive scan of the counts; off[nwin] = total), gather
-    size_t tb = 0;
-    HIPCHK(rocprim::exclusive_scan(nullptr, tb, cnt, off, 0ull, nwin + 1, rocprim::plus<unsigned long long>(), c->st));
-    void *tmp;
-    if ((r = dscratch(c, 4, tb, &tmp))) return r;
-    HIPCHK(rocprim::exclusive_scan(tmp, tb, cnt, off, 0ull, nwin + 1, rocprim::plus<unsigned long long>(), c->st));
+    r = ROCPRIM_RUN(c, DS_SCAN_TMP, rocprim::exclusive_scan(tmp, tb, cnt, off, 0ull, nwin + 1, rocprim::plus<unsigned long long>(), c->st));
+    if (r) return r;
     if (nwin) {
         const size_t glds = P.relabeled ? (size_t)P.V * 2 : 0;
         (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&k_ew_gather), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -2438,11 +2448,8 @@ int ed_run(bpe_gpu_ctx *c, const EwPlan &P, const uint32_t *d_img, uint32_t halo
         HIPCHK(hipStreamSynchronize(c->st));
         tph[2] = now_ms();
     }
-    size_t tb = 0;
-    HIPCHK(rocprim::exclusive_scan(nullptr, tb, cnt, off, 0ull, nwin + 1, rocprim::plus<unsigned long long>(), c->st));
-    void *tmp;
-    if ((r = dscratch(c, 4, tb, &tmp))) return r;
-    HIPCHK(rocprim::exclusive_scan(tmp, tb, cnt, off, 0ull, nwin + 1, rocprim::plus<unsigned long long>(), c->st));
+    r = ROCPRIM_RUN(c, DS_SCAN_TMP, rocprim::exclusive_scan(tmp, tb, cnt, off, 0ull, nwin + 1, rocprim::plus<unsigned long long>(), c->st));
+    if (r) return r;
     k_ed_offsets<<<(uint32_t)((ndocs + 256) / 256), 256, 0, c->st>>>(d_doc, ndocs, n, core, off, nwin, rel, d_idoff);
     HIPCHK(hipGetLastError());
     if (nwin) {
@@ -2834,7 +2841,7 @@ int bpe_gpu_encode(bpe_gpu_ctx *c, const uint32_t *pairs, size_t n_merges) {
         const EwPlan P = ew_plan(pairs, n_merges, c->ew_stage);
         if (P.ok) {
             void *d_img;
-            if ((r = dscratch(c, 7, P.words * 4, &d_img))) return r;
+            if ((r = dscratch(c, DS_EW_TABLES, P.words * 4, &d_img))) return r;
             HIPCHK(hipMemcpyAsync(d_img, c->ew_stage.data(), P.words * 4, hipMemcpyHostToDevice, c->st));
             bool ok = false;
             int pass = 0;
@@ -2966,10 +2973,12 @@ static int decode_run(bpe_gpu_ctx *c, const uint32_t *ids, size_t len, const uin
     // sum over the ids (rocprim scan), the byte gather (k_dec_expand)
     const uint32_t V0 = (uint32_t)(256 + n_merges), V = V0 + S;
     int r;
-    void *p[7];
-    if ((r = dscratch(c, 0, std::max<size_t>(len, 1) * 4, &p[0])) || (r = dscratch(c, 1, std::max<size_t>(n_merges, 1) * 8, &p[1])) ||
-        (r = dscratch(c, 2, (size_t)V * 8, &p[2])) || (r = dscratch(c, 3, (len + 1) * 8, &p[3])) ||
-        (r = dscratch(c, 6, 64, &p[6])))
+    uint32_t *d_ids, *d_pairs, *d_err;
+    uint64_t *d_elen, *d_off;
+    if ((r = dscratch(c, DS_DEC_IDS, std::max<size_t>(len, 1) * 4, &d_ids)) ||
+        (r = dscratch(c, DS_DEC_PAIRS, std::max<size_t>(n_merges, 1) * 8, &d_pairs)) ||
+        (r = dscratch(c, DS_DEC_ELEN, (size_t)V * 8, &d_elen)) || (r = dscratch(c, DS_DEC_OFF, (len + 1) * 8, &d_off)) ||
+        (r = dscratch(c, DS_DEC_ERR, 64, &d_err)))
         return r;
     uint8_t *d_sp = nullptr;
     uint32_t *d_soff = nullptr;
@@ -2980,15 +2989,10 @@ static int decode_run(bpe_gpu_ctx *c, const uint32_t *ids, size_t len, const uin
         sp_off[j + 1] = sp_off[j] + sp->len[j];
     }
     if (S) {
-        void *a, *b;
-        if ((r = dscratch(c, 47, sp_off[S], &a)) || (r = dscratch(c, 48, (S + 1) * 4, &b))) return r;
-        d_sp = (uint8_t *)a;
-        d_soff = (uint32_t *)b;
+        if ((r = dscratch(c, DS_SP_DEC_BYTES, sp_off[S], &d_sp)) || (r = dscratch(c, DS_SP_DEC_OFF, (S + 1) * 4, &d_soff))) return r;
         HIPCHK(hipMemcpyAsync(d_sp, sp->bytes, sp_off[S], hipMemcpyHostToDevice, c->st));
         HIPCHK(hipMemcpyAsync(d_soff, sp_off.data(), (S + 1) * 4, hipMemcpyHostToDevice, c->st));
     }
-    uint32_t *d_ids = (uint32_t *)p[0], *d_pairs = (uint32_t *)p[1], *d_err = (uint32_t *)p[6];
-    uint64_t *d_elen = (uint64_t *)p[2], *d_off = (uint64_t *)p[3];
     HIPCHK(hipMemsetAsync(d_err, 0, 8, c->st));
     if (len) HIPCHK(hipMemcpyAsync(d_ids, ids, len * 4, hipMemcpyHostToDevice, c->st));
     if (n_merges) HIPCHK(hipMemcpyAsync(d_pairs, pairs, n_merges * 8, hipMemcpyHostToDevice, c->st));
@@ -3010,10 +3014,8 @@ static int decode_run(bpe_gpu_ctx *c, const uint32_t *ids, size_t len, const uin
     HIPCHK(hipGetLastError());
     auto lens = rocprim::make_transform_iterator(rocprim::make_counting_iterator<uint64_t>(0),
                                                  DecLen{d_ids, d_elen, (uint64_t)len, V});
-    size_t tb = 0;
-    HIPCHK(rocprim::exclusive_scan(nullptr, tb, lens, d_off, (uint64_t)0, len + 1, rocprim::plus<uint64_t>(), c->st));
-    if ((r = dscratch(c, 4, tb, &p[4]))) return r;
-    HIPCHK(rocprim::exclusive_scan(p[4], tb, lens, d_off, (uint64_t)0, len + 1, rocprim::plus<uint64_t>(), c->st));
+    r = ROCPRIM_RUN(c, DS_SCAN_TMP, rocprim::exclusive_scan(tmp, tb, lens, d_off, (uint64_t)0, len + 1, rocprim::plus<uint64_t>(), c->st));
+    if (r) return r;
     uint32_t err[2] = {0, 0};
     uint64_t total = 0;
     HIPCHK(hipMemcpyAsync(err, d_err, 8, hipMemcpyDeviceToHost, c->st));
@@ -3025,11 +3027,12 @@ static int decode_run(bpe_gpu_ctx *c, const uint32_t *ids, size_t len, const uin
     if (!out) return 0;
     if (cap < total) return fail(BPE_GPU_EINVAL, "decode: output buffer too small");
     if (len == 0 || total == 0) return 0;
-    if ((r = dscratch(c, 5, total, &p[5]))) return r;
-    if (S) k_sp_dec_expand<<<1024, 256, 0, c->st>>>(d_ids, len, d_pairs, d_elen, d_off, V0, d_sp, d_soff, (uint8_t *)p[5]);
-    else k_dec_expand<<<1024, 256, 0, c->st>>>(d_ids, len, d_pairs, d_elen, d_off, (uint8_t *)p[5]);
+    uint8_t *d_out;
+    if ((r = dscratch(c, DS_DEC_OUT, total, &d_out))) return r;
+    if (S) k_sp_dec_expand<<<1024, 256, 0, c->st>>>(d_ids, len, d_pairs, d_elen, d_off, V0, d_sp, d_soff, d_out);
+    else k_dec_expand<<<1024, 256, 0, c->st>>>(d_ids, len, d_pairs, d_elen, d_off, d_out);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out, p[5], total, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipMemcpyAsync(out, d_out, total, hipMemcpyDeviceToHost, c->st));
     HIPCHK(hipStreamSynchronize(c->st));
     return 0;
 }
@@ -3256,7 +3259,7 @@ int bpe_gpu_trim(bpe_gpu_ctx *c) {
     c->sp_cap = 0;
     c->sp_S = 0;
     c->sp_M = 0;
-    for (int k = 0; k < (int)(sizeof c->dscr / sizeof c->dscr[0]); k++) {
+    for (int k = 0; k < DS_COUNT; k++) {
         if (c->dscr[k]) (void)hipFree(c->dscr[k]);
         c->dscr[k] = nullptr;
         c->dscr_cap[k] = 0;
@@ -3343,7 +3346,7 @@ static int encode_docs_run(bpe_gpu_ctx *c, const uint64_t *doc_off, size_t ndocs
     const double t_plan = now_ms();
     if (P.ok) {
         void *d_img;
-        if ((r = dscratch(c, 7, P.words * 4, &d_img))) return r;
+        if ((r = dscratch(c, DS_EW_TABLES, P.words * 4, &d_img))) return r;
         HIPCHK(hipMemcpyAsync(d_img, c->ew_stage.data(), P.words * 4, hipMemcpyHostToDevice, c->st));
         halo = ew_halo();
         core = EW_W - 2 * halo;
@@ -3463,607 +3466,6 @@ int bpe_gpu_encode_docs(bpe_gpu_ctx *c, const uint64_t *doc_off, size_t ndocs, c
     return encode_docs_run(c, doc_off, ndocs, pairs, n_merges, t_chk);
 }
 
-// ------------------------------------------------ pieces of the resident bytes (split.hip)
-
-int bpe_gpu_split_rule(int preset, uint8_t *cls, uint16_t *brk) {
-    if (!cls || !brk) return fail(BPE_GPU_EINVAL, "split_rule: bad argument");
-    memset(cls, 0, 256);
-    memset(brk, 0, 16 * sizeof(uint16_t));
-    if (preset == BPE_SPLIT_LINES) {
-        cls['\n'] = 1;
-        brk[1] = 0x3;
-        return 0;
-    }
-    if (preset == BPE_SPLIT_GPT2) return fail(BPE_GPU_EINVAL, "split_rule: BPE_SPLIT_GPT2 has no tables (bpe_gpu_split_preset)");
-    if (preset == BPE_SPLIT_GPT2_UNICODE)
-        return fail(BPE_GPU_EINVAL, "split_rule: BPE_SPLIT_GPT2_UNICODE has no tables (bpe_gpu_split_preset)");
-    if (preset == BPE_SPLIT_CL100K) return fail(BPE_GPU_EINVAL, "split_rule: BPE_SPLIT_CL100K has no tables (bpe_gpu_split_preset)");
-    if (preset != BPE_SPLIT_WORDS) return fail(BPE_GPU_EINVAL, "split_rule: no such preset");
-    for (int b = 0; b < 256; b++)
-        cls[b] = (b >= 'A' && b <= 'Z') || (b >= 'a' && b <= 'z') || b >= 0x80 ? 1
-                 : b >= '0' && b <= '9'                                        ? 2
-                 : b == ' '                                                    ? 3
-                 : b >= '\t' && b <= '\r'                                      ? 4
-                                                                               : 0;
-    for (int p = 0; p < 5; p++) brk[p] = (uint16_t)(0x1F & ~(1 << p));
-    brk[3] = 1 << 4;
-    return 0;
-}
-
-int bpe_gpu_split_info(uint64_t *out4) {
-    if (!out4) return BPE_GPU_EINVAL;
-    out4[0] = SP_TILE;
-    out4[1] = (uint64_t)SP_TILE * SP_GRID;
-    out4[2] = out4[3] = 0;
-    return 0;
-}
-
-// workgroups of the per-match / per-id kernels of special.hip (they stride)
-static uint32_t sx_grid(uint64_t items) {
-    return (uint32_t)std::min<uint64_t>(std::max<uint64_t>((items + SX_T - 1) / SX_T, 1), SX_GRID);
-}
-
-// The special passes of a split (special.hip).  sp_find: the matches, *M of them, their list in scratch slot 40
-// and the cover bitmap in slot 39; it runs after the marking kernel, or before it for BPE_SPLIT_CL100K, whose
-// marking kernel reads the bitmap.  sp_patch, between the marking kernel and the count scan when there are
-// matches: patch, recount and sort; *sorted the list by start (scratch slot 41).
-static int sp_find(bpe_gpu_ctx *c, const SpSet *sp, uint64_t n, uint64_t ntiles, uint32_t grid, uint32_t *M, uint64_t *info) {
-    int r;
-    void *pset, *pcov, *pctl, *plist = nullptr;
-    const size_t cov_bytes = ntiles * SP_T * 2;  // a bit per byte of the whole tiles
-    if ((r = dscratch(c, 38, sizeof(SpSet), &pset)) || (r = dscratch(c, 39, cov_bytes, &pcov)) || (r = dscratch(c, 43, 64, &pctl)))
-        return r;
-    uint32_t *ctl = (uint32_t *)pctl;
-    HIPCHK(hipMemcpyAsync(pset, sp, sizeof(SpSet), hipMemcpyHostToDevice, c->st));
-    HIPCHK(hipMemsetAsync(pcov, 0, cov_bytes, c->st));
-    // room for a match every 256 bytes; a text with more runs the pass again with the room it counted
-    uint64_t cap = n / 256 + 1024;
-    uint32_t found = 0;
-    for (int pass = 1;; pass++) {
-        if ((r = dscratch(c, 40, cap * 8, &plist))) return r;
-        HIPCHK(hipMemsetAsync(ctl, 0, 64, c->st));
-        k_sp_find<<<grid, SP_T, 0, c->st>>>(c->h.bytes, n, ntiles, (const SpSet *)pset, (uint32_t *)pcov,
-                                            (unsigned long long *)plist, (uint32_t)std::min<uint64_t>(cap, 0xFFFFFFFFull), ctl);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(&found, ctl, 4, hipMemcpyDeviceToHost, c->st));
-        HIPCHK(hipStreamSynchronize(c->st));
-        info[2] = (uint64_t)pass;
-        if (found <= cap) break;
-        if (pass == 2) return fail(BPE_GPU_EINTERNAL, "split_special: the second find pass counted more matches than the first");
-        cap = found;
-    }
-    info[1] = found;
-    info[3] = cap;
-    *M = found;
-    return 0;
-}
-
-static int sp_patch(bpe_gpu_ctx *c, int gpt2, uint64_t n, uint64_t ntiles, uint32_t grid, uint16_t *mask, uint32_t *wcnt,
-                    uint32_t found, unsigned long long **sorted) {
-    int r;
-    void *pset = c->dscr[38], *pcov = c->dscr[39], *plist = c->dscr[40], *psort, *tmp;
-    *sorted = nullptr;
-    if (!found) return 0;
-    k_sp_patch<<<sx_grid(found), SX_T, 0, c->st>>>(c->h.bytes, n, (const unsigned long long *)plist, found, (const SpSet *)pset,
-                                                  (const uint32_t *)pcov, (uint32_t *)mask, gpt2);
-    HIPCHK(hipGetLastError());
-    k_sp_recount<<<grid, SP_T, 0, c->st>>>(mask, ntiles, wcnt);
-    HIPCHK(hipGetLastError());
-    if ((r = dscratch(c, 41, (size_t)found * 8, &psort))) return r;
-    size_t tb = 0;
-    HIPCHK(rocprim::radix_sort_keys(nullptr, tb, (unsigned long long *)plist, (unsigned long long *)psort, found, 8, 40, c->st));
-    if ((r = dscratch(c, 42, tb, &tmp))) return r;
-    HIPCHK(rocprim::radix_sort_keys(tmp, tb, (unsigned long long *)plist, (unsigned long long *)psort, found, 8, 40, c->st));
-    *sorted = (unsigned long long *)psort;
-    return 0;
-}
-
-// the body of bpe_gpu_split (R: the tables) and of bpe_gpu_split_preset's BPE_SPLIT_GPT2 and BPE_SPLIT_GPT2_UNICODE
-// and BPE_SPLIT_CL100K (R == nullptr; gpt2: 1 the first, 2 the second, 3 the third; sp_patch hands 1 and 2 to
-// k_sp_patch; 3 has read the matches while marking): all but the marking launches is one code, so the offsets and
-// their lifetime are the same whichever kernel marked the starts.
-// sp: the specials of bpe_gpu_split_special (nullptr: none, and nothing but the launches below runs)
-static int split_run(bpe_gpu_ctx *c, const SplitRule *R, size_t *ndocs, const SpSet *sp = nullptr, int gpt2 = 0) {
-    if (!R && !gpt2) gpt2 = 1;
-    HIPCHK(hipSetDevice(c->dev));
-    c->split_ready = false;
-    c->ts_ready = false;  // bpe_gpu_train_split's results describe the offsets replaced here
-    c->sp_S = 0;          // ... and so do the specials and their pieces
-    c->sp_M = 0;
-    uint64_t sp_info[4] = {sp ? sp->S : 0u, 0, 0, 0};
-    uint32_t sp_M = 0;
-    unsigned long long *sp_sorted = nullptr;
-    const uint64_t n = c->n0, ntiles = (n + SP_TILE - 1) / SP_TILE, nwt = ntiles * (SP_T / 64);
-    unsigned long long total = 0;
-    uint16_t *mask = nullptr;
-    unsigned long long *woff = nullptr;
-    int r;
-    if (n) {
-        void *tbl = nullptr, *pm, *pc, *tmp;
-        // counts [nwt + 1] (the last one 0) and their scan [nwt + 1] in one slot
-        if ((R && (r = dscratch(c, 12, SP_TBL * 4, &tbl))) || (r = dscratch(c, 13, ntiles * SP_T * 2, &pm)) ||
-            (r = dscratch(c, 14, (nwt + 1) * 8 + ((nwt + 1) * 4 + 7) / 8 * 8, &pc)))
-            return r;
-        mask = (uint16_t *)pm;
-        woff = (unsigned long long *)pc;
-        uint32_t *wcnt = (uint32_t *)(woff + nwt + 1);
-        const uint32_t grid = (uint32_t)std::min<uint64_t>(ntiles, SP_GRID);
-        HIPCHK(hipMemsetAsync(wcnt + nwt, 0, 4, c->st));
-        if (sp && gpt2 == 3 && (r = sp_find(c, sp, n, ntiles, grid, &sp_M, sp_info))) return r;
-        if (R) {
-            k_split_table<<<SP_TBL / SP_T, SP_T, 0, c->st>>>(*R, (uint32_t *)tbl);
-            HIPCHK(hipGetLastError());
-            k_split_mark<<<grid, SP_T, 0, c->st>>>(c->h.bytes, n, (const uint32_t *)tbl, ntiles, mask, wcnt);
-        } else if (gpt2 == 3) {
-            // the effects of the wave tiles on the three chains, their scan, and the marks (split.hip).  One scan
-            // serves both directions: sum_f[nwt], a reset (the summary kernel writes it), sum_b[nwt] (the tiles in
-            // reverse order)
-            void *pcl, *ptmp;
-            const size_t cnt = 2 * nwt + 1;
-            if ((r = dscratch(c, 49, 2 * cnt * 4, &pcl))) return r;
-            uint32_t *sum = (uint32_t *)pcl, *in = sum + cnt;
-            const uint32_t *cover = sp ? (const uint32_t *)c->dscr[39] : nullptr;
-            k_cl_summary<<<grid, SP_T, 0, c->st>>>(c->h.bytes, n, ntiles, cover, sum, sum + nwt + 1);
-            HIPCHK(hipGetLastError());
-            size_t tb = 0;
-            HIPCHK(rocprim::exclusive_scan(nullptr, tb, sum, in, CL_RESET, cnt, ClCompose(), c->st));
-            if ((r = dscratch(c, 50, tb, &ptmp))) return r;
-            HIPCHK(rocprim::exclusive_scan(ptmp, tb, sum, in, CL_RESET, cnt, ClCompose(), c->st));
-            k_split_mark_cl100k<<<grid, SP_T, 0, c->st>>>(c->h.bytes, n, ntiles, cover, in, in + nwt + 1, mask, wcnt);
-        } else if (gpt2 == 2) {
-            k_split_mark_gpt2u<<<grid, SP_T, 0, c->st>>>(c->h.bytes, n, ntiles, mask, wcnt);
-        } else {
-            k_split_mark_gpt2<<<grid, SP_T, 0, c->st>>>(c->h.bytes, n, ntiles, mask, wcnt);
-        }
-        HIPCHK(hipGetLastError());
-        if (sp && gpt2 != 3 && (r = sp_find(c, sp, n, ntiles, grid, &sp_M, sp_info))) return r;
-        if (sp && (r = sp_patch(c, R || gpt2 == 3 ? 0 : gpt2, n, ntiles, grid, mask, wcnt, sp_M, &sp_sorted))) return r;
-        size_t tb = 0;
-        HIPCHK(rocprim::exclusive_scan(nullptr, tb, wcnt, woff, 0ull, nwt + 1, rocprim::plus<unsigned long long>(), c->st));
-        if ((r = dscratch(c, 15, tb, &tmp))) return r;
-        HIPCHK(rocprim::exclusive_scan(tmp, tb, wcnt, woff, 0ull, nwt + 1, rocprim::plus<unsigned long long>(), c->st));
-        HIPCHK(hipMemcpyAsync(&total, woff + nwt, 8, hipMemcpyDeviceToHost, c->st));
-        HIPCHK(hipStreamSynchronize(c->st));
-        if (total == 0 || total > n) return fail(BPE_GPU_EINTERNAL, "split: piece count out of range");
-    }
-    if (c->split_cap < total + 1) {
-        HIPCHK(hipStreamSynchronize(c->st));
-        if (c->d_split) (void)hipFree(c->d_split);
-        c->d_split = nullptr;
-        c->split_cap = 0;
-        const size_t cap = std::max<size_t>(total + 1, 32);
-        hipError_t e = hipMalloc(&c->d_split, cap * 8);
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(BPE_GPU_ENOMEM, "split: hipMalloc of the offsets", e);
-        }
-        c->split_cap = cap;
-    }
-    if (n) {
-        const uint32_t grid = (uint32_t)std::min<uint64_t>(ntiles, SP_GRID);
-        k_split_emit<<<grid, SP_T, 0, c->st>>>(mask, woff, ntiles, n, c->d_split);
-        HIPCHK(hipGetLastError());
-    } else {
-        HIPCHK(hipMemsetAsync(c->d_split, 0, 8, c->st));
-    }
-    if (sp_M) {  // the matches' starts as piece indices: the list that stays
-        if (c->sp_cap < sp_M) {
-            HIPCHK(hipStreamSynchronize(c->st));
-            if (c->d_sp_pieces) (void)hipFree(c->d_sp_pieces);
-            c->d_sp_pieces = nullptr;
-            c->sp_cap = 0;
-            hipError_t e = hipMalloc(&c->d_sp_pieces, (size_t)sp_M * 8);
-            if (e != hipSuccess) {
-                (void)hipGetLastError();
-                return fail(BPE_GPU_ENOMEM, "split_special: hipMalloc of the special pieces", e);
-            }
-            c->sp_cap = sp_M;
-        }
-        uint32_t *ctl = (uint32_t *)c->dscr[43], bad = 0;
-        k_sp_pieces<<<sx_grid(sp_M), SX_T, 0, c->st>>>(sp_sorted, sp_M, c->d_split, total, c->d_sp_pieces, ctl + 1);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(&bad, ctl + 1, 4, hipMemcpyDeviceToHost, c->st));
-        HIPCHK(hipStreamSynchronize(c->st));
-        if (bad) return fail(BPE_GPU_EINTERNAL, "split_special: a match does not start a piece");
-    }
-    HIPCHK(hipStreamSynchronize(c->st));
-    c->sp_S = sp ? sp->S : 0u;
-    c->sp_M = sp_M;
-    memcpy(c->sp_info, sp_info, sizeof sp_info);
-    c->split_n = total;
-    c->split_ready = true;
-    *ndocs = (size_t)total;
-    return 0;
-}
-
-int bpe_gpu_split(bpe_gpu_ctx *c, const uint8_t *cls, const uint16_t *brk, size_t *ndocs) {
-    if (!c || !cls || !brk || !ndocs) return BPE_GPU_EINVAL;
-    if (!c->loaded) return fail(BPE_GPU_ESTATE, "split before load");
-    SplitRule R;
-    for (int b = 0; b < 256; b++)
-        if ((R.cls[b] = cls[b]) > 15) return fail(BPE_GPU_EINVAL, "split: a class above 15");
-    memcpy(R.brk, brk, sizeof R.brk);
-    return split_run(c, &R, ndocs);
-}
-
-int bpe_gpu_split_preset(bpe_gpu_ctx *c, int preset, size_t *ndocs) {
-    if (!c || !ndocs) return BPE_GPU_EINVAL;
-    if (preset != BPE_SPLIT_LINES && preset != BPE_SPLIT_WORDS && preset != BPE_SPLIT_GPT2 && preset != BPE_SPLIT_GPT2_UNICODE &&
-        preset != BPE_SPLIT_CL100K)
-        return fail(BPE_GPU_EINVAL, "split_preset: no such preset");
-    if (preset == BPE_SPLIT_GPT2 || preset == BPE_SPLIT_GPT2_UNICODE || preset == BPE_SPLIT_CL100K) {
-        if (!c->loaded) return fail(BPE_GPU_ESTATE, "split before load");
-        return split_run(c, nullptr, ndocs, nullptr, preset == BPE_SPLIT_GPT2 ? 1 : preset == BPE_SPLIT_GPT2_UNICODE ? 2 : 3);
-    }
-    uint8_t cls[256];
-    uint16_t brk[16];
-    const int r = bpe_gpu_split_rule(preset, cls, brk);
-    return r ? r : bpe_gpu_split(c, cls, brk, ndocs);
-}
-
-int bpe_gpu_split_special(bpe_gpu_ctx *c, int preset, const uint8_t *cls, const uint16_t *brk,
-                          const bpe_gpu_specials *specials, size_t *ndocs) {
-    if (!c || !ndocs) return BPE_GPU_EINVAL;
-    if (preset < 0 && (!cls || !brk)) return fail(BPE_GPU_EINVAL, "split_special: no preset and no tables");
-    if (preset >= 0 && preset != BPE_SPLIT_LINES && preset != BPE_SPLIT_WORDS && preset != BPE_SPLIT_GPT2 &&
-        preset != BPE_SPLIT_GPT2_UNICODE && preset != BPE_SPLIT_CL100K)
-        return fail(BPE_GPU_EINVAL, "split_special: no such preset");
-    char msg[400];
-    if (bpe_specials_check(specials, msg, sizeof msg)) return fail(BPE_GPU_EINVAL, msg);
-    if (!c->loaded) return fail(BPE_GPU_ESTATE, "split before load");
-    const size_t S = specials ? specials->count : 0;
-    if (S == 0) return preset < 0 ? bpe_gpu_split(c, cls, brk, ndocs) : bpe_gpu_split_preset(c, preset, ndocs);
-    // the set as the device reads it: in lexicographic order (no special is a prefix of another, so the first
-    // difference decides), with the first-byte set
-    std::vector<SpSet> hs(1);
-    SpSet &H = hs[0];
-    memset(&H, 0, sizeof H);
-    std::vector<size_t> off(S + 1, 0);
-    for (size_t j = 0; j < S; j++) off[j + 1] = off[j] + specials->len[j];
-    std::vector<uint32_t> order(S);
-    for (size_t j = 0; j < S; j++) order[j] = (uint32_t)j;
-    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
-        const int d = memcmp(specials->bytes + off[a], specials->bytes + off[b], std::min(specials->len[a], specials->len[b]));
-        return d ? d < 0 : specials->len[a] < specials->len[b];
-    });
-    for (size_t k = 0; k < S; k++) {
-        const uint32_t j = order[k], L = specials->len[j];
-        memcpy(H.txt + k * SX_LEN, specials->bytes + off[j], L);
-        H.len[k] = (uint8_t)(L - 1);
-        H.idx[k] = (uint8_t)j;
-        H.lenj[j] = (uint8_t)(L - 1);
-        const uint8_t b = specials->bytes[off[j]];
-        H.first[b >> 5] |= 1u << (b & 31);
-    }
-    H.S = (uint32_t)S;
-    SplitRule R;
-    if (preset == BPE_SPLIT_GPT2) return split_run(c, nullptr, ndocs, &H, 1);
-    if (preset == BPE_SPLIT_GPT2_UNICODE) return split_run(c, nullptr, ndocs, &H, 2);
-    if (preset == BPE_SPLIT_CL100K) return split_run(c, nullptr, ndocs, &H, 3);
-    if (preset >= 0) {
-        uint8_t pc[256];
-        const int r = bpe_gpu_split_rule(preset, pc, R.brk);
-        if (r) return r;
-        memcpy(R.cls, pc, 256);
-    } else {
-        for (int b = 0; b < 256; b++)
-            if ((R.cls[b] = cls[b]) > 15) return fail(BPE_GPU_EINVAL, "split: a class above 15");
-        memcpy(R.brk, brk, sizeof R.brk);
-    }
-    return split_run(c, &R, ndocs, &H);
-}
-
-int bpe_gpu_split_special_info(bpe_gpu_ctx *c, uint64_t *out4) {
-    if (!c || !out4) return BPE_GPU_EINVAL;
-    if (!c->loaded || !c->split_ready) return fail(BPE_GPU_ESTATE, "no split: split first");
-    memset(out4, 0, 4 * sizeof(uint64_t));
-    if (c->sp_S) memcpy(out4, c->sp_info, sizeof c->sp_info);
-    return 0;
-}
-
-int bpe_gpu_fetch_special_pieces(bpe_gpu_ctx *c, uint64_t *piece, uint32_t *index, size_t cap, size_t *count) {
-    if (!c || !count) return BPE_GPU_EINVAL;
-    if (!c->loaded || !c->split_ready) return fail(BPE_GPU_ESTATE, "no special pieces: split first");
-    HIPCHK(hipSetDevice(c->dev));
-    const uint64_t M = c->sp_S ? c->sp_M : 0;
-    *count = (size_t)M;
-    const size_t k = std::min<size_t>(cap, (size_t)M);
-    if (!k || (!piece && !index)) return 0;
-    std::vector<unsigned long long> h(k);
-    const int r = d2h_staged(c, h.data(), c->d_sp_pieces, k * 8);
-    if (r) return r;
-    for (size_t m = 0; m < k; m++) {
-        if (piece) piece[m] = h[m] >> 8;
-        if (index) index[m] = (uint32_t)(h[m] & 0xFFull);
-    }
-    return 0;
-}
-
-int bpe_gpu_fetch_split_offsets(bpe_gpu_ctx *c, uint64_t *out, size_t cap, size_t *count) {
-    if (!c || !count) return BPE_GPU_EINVAL;
-    if (!c->loaded || !c->split_ready) return fail(BPE_GPU_ESTATE, "no split offsets: split first");
-    HIPCHK(hipSetDevice(c->dev));
-    *count = c->split_n + 1;
-    const size_t k = out ? std::min<size_t>(cap, c->split_n + 1) : 0;
-    if (k) return d2h_staged(c, out, c->d_split, k * 8);
-    return 0;
-}
-
-int bpe_gpu_encode_split(bpe_gpu_ctx *c, const uint32_t *pairs, size_t n_merges) {
-    if (!c || (!pairs && n_merges)) return BPE_GPU_EINVAL;
-    if (!c->loaded) return fail(BPE_GPU_ESTATE, "encode before load");
-    if (!c->split_ready) return fail(BPE_GPU_ESTATE, "encode_split: no split of the loaded bytes");
-    if (n_merges > 0xFFFFFEFFull) return fail(BPE_GPU_ERANGE, "merge list too long");
-    const uint64_t M = c->sp_S ? c->sp_M : 0;
-    if (M && n_merges + 256 + c->sp_S > 0xFFFFFFFFull) return fail(BPE_GPU_ERANGE, "merge list too long for the specials' ids");
-    int r = encode_docs_run(c, nullptr, c->split_n, pairs, n_merges, now_ms());
-    if (r || !M) return r;
-    // The post-pass (special.hip): whichever path left ids_out / d_idoff, every special piece keeps one id,
-    // 256 + n_merges + j, and the ids and offsets after it move down.
-    const double t0 = now_ms();
-    const uint64_t len = c->ids_len, ndocs = c->split_n;
-    void *pist, *prem, *prs, *tmp;
-    if ((r = dscratch(c, 44, M * 8, &pist)) || (r = dscratch(c, 45, (M + 1) * 8, &prem)) || (r = dscratch(c, 46, (M + 1) * 8, &prs)))
-        return r;
-    uint64_t *ist = (uint64_t *)pist, *rem = (uint64_t *)prem, *rsum = (uint64_t *)prs;
-    k_sp_idlen<<<sx_grid(M + 1), SX_T, 0, c->st>>>(c->d_sp_pieces, (uint32_t)M, c->d_idoff, ist, rem);
-    HIPCHK(hipGetLastError());
-    size_t tb = 0;
-    HIPCHK(rocprim::exclusive_scan(nullptr, tb, rem, rsum, (uint64_t)0, M + 1, rocprim::plus<uint64_t>(), c->st));
-    if ((r = dscratch(c, 42, tb, &tmp))) return r;
-    HIPCHK(rocprim::exclusive_scan(tmp, tb, rem, rsum, (uint64_t)0, M + 1, rocprim::plus<uint64_t>(), c->st));
-    uint64_t removed = 0;
-    HIPCHK(hipMemcpyAsync(&removed, rsum + M, 8, hipMemcpyDeviceToHost, c->st));
-    HIPCHK(hipStreamSynchronize(c->st));
-    if (removed > len || len - removed < M) return fail(BPE_GPU_EINTERNAL, "encode_split: the special pieces hold more ids than there are");
-    uint32_t *ids2;
-    uint64_t *idoff2;
-    if ((r = dalloc(c, &ids2, len - removed, false)) || (r = dalloc(c, &idoff2, ndocs + 1, false))) return r;
-    k_sp_ids<<<sx_grid(len), SX_T, 0, c->st>>>(c->h.ids_out, len, c->d_sp_pieces, (uint32_t)M, ist, rsum,
-                                              (uint32_t)(256 + n_merges), ids2);
-    HIPCHK(hipGetLastError());
-    k_sp_idoff<<<sx_grid(ndocs + 1), SX_T, 0, c->st>>>(c->d_idoff, ndocs, c->d_sp_pieces, (uint32_t)M, rsum, idoff2);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipStreamSynchronize(c->st));
-    c->h.ids_out = ids2;
-    c->d_idoff = idoff2;
-    c->ids_len = len - removed;
-    const double ms = now_ms() - t0;
-    c->stats.n_out = c->ids_len;
-    c->stats.occurrences = c->n0 - std::min<uint64_t>(c->n0, c->ids_len);
-    c->stats.ms_train += ms;
-    c->stats.ms_total += ms;
-    return 0;
-}
-
-// ------------------------------------------------ training on the pieces (train_split.hip)
-
-// workgroups for `items` elements at `per` of them per thread, TS_GRID at most (the kernels stride)
-static uint32_t ts_grid(uint64_t items, uint32_t per = 1) {
-    const uint64_t chunk = (uint64_t)TS_T * per;
-    return (uint32_t)std::min<uint64_t>(std::max<uint64_t>((items + chunk - 1) / chunk, 1), TS_GRID);
-}
-
-// the control words on the host (one synchronisation)
-static int ts_read_ctl(bpe_gpu_ctx *c, const uint32_t *ctl, uint32_t *hc) {
-    HIPCHK(hipMemcpyAsync(hc, ctl, 16 * 4, hipMemcpyDeviceToHost, c->st));
-    HIPCHK(hipStreamSynchronize(c->st));
-    return 0;
-}
-
-// Stage A: the pieces as weighted entries in start order.  Leaves the piece indices and counts in scratch
-// slots 21 / 22, starts and lengths in 23 / 24, the scanned lengths in 25; *E entries, *T bytes of entries.
-static int ts_piece_table(bpe_gpu_ctx *c, uint32_t *ctl, uint64_t *E, uint64_t *T, uint64_t *nlong, uint64_t *slots) {
-    const uint64_t P = c->split_n;
-    const uint64_t *off = c->d_split;
-    uint32_t hc[16];
-    int r;
-    // the table starts small (text has few distinct pieces) and grows fourfold when a probe chain runs out;
-    // at 2 P slots or more a chain of TS_PROBE is a defect of the hash, not load
-    const uint64_t smax = std::max<uint64_t>(pow2_at_least(2 * P), 1024) * 16;
-    const int knob = getenv_int("BPE_TS_SLOTS", 0);
-    uint64_t S = knob > 0 ? pow2_at_least(std::max(knob, 64)) : std::min<uint64_t>(std::max<uint64_t>(pow2_at_least(2 * P), 1024), 1u << 22);
-    void *pslot, *pcnt;
-    for (;;) {
-        if ((r = dscratch(c, 16, S * 8, &pslot)) || (r = dscratch(c, 17, S * 4, &pcnt))) return r;
-        HIPCHK(hipMemsetAsync(pslot, 0xFF, S * 8, c->st));
-        HIPCHK(hipMemsetAsync(pcnt, 0, S * 4, c->st));
-        HIPCHK(hipMemsetAsync(ctl, 0, 16 * 4, c->st));
-        k_ts_insert<<<ts_grid(P, 8), TS_T, 0, c->st>>>(c->h.bytes, off, P, (unsigned long long *)pslot, (uint32_t *)pcnt, S - 1, ctl);
-        HIPCHK(hipGetLastError());
-        if ((r = ts_read_ctl(c, ctl, hc))) return r;
-        if (!hc[TSC_FULL]) break;
-        if (S >= smax) return fail(BPE_GPU_EINTERNAL, "train_split: the piece table is full at its largest size");
-        S *= 4;
-    }
-    *slots = S;
-    *nlong = hc[TSC_LONG];
-    uint64_t ne = (uint64_t)hc[TSC_LONG] + hc[TSC_CLAIMED];
-    if (ne == 0 || ne > P) return fail(BPE_GPU_EINTERNAL, "train_split: entry count out of range");
-    void *k0, *v0, *k1, *v1, *est, *elen, *eoff, *tmp;
-    if ((r = dscratch(c, 19, ne * 4, &k0)) || (r = dscratch(c, 20, ne * 4, &v0)) || (r = dscratch(c, 21, ne * 4, &k1)) ||
-        (r = dscratch(c, 22, ne * 4, &v1)) || (r = dscratch(c, 23, ne * 8, &est)) || (r = dscratch(c, 24, (ne + 1) * 4, &elen)) ||
-        (r = dscratch(c, 25, (ne + 1) * 4, &eoff)))
-        return r;
-    k_ts_collect_slots<<<ts_grid(S), TS_T, 0, c->st>>>((const unsigned long long *)pslot, (const uint32_t *)pcnt, S, ctl,
-                                                      (uint32_t *)k0, (uint32_t *)v0, ne);
-    HIPCHK(hipGetLastError());
-    if (hc[TSC_LONG]) {
-        k_ts_collect_long<<<ts_grid(P), TS_T, 0, c->st>>>(off, P, ctl, (uint32_t *)k0, (uint32_t *)v0, ne);
-        HIPCHK(hipGetLastError());
-    }
-    // After a split with specials their pieces are no part of the corpus: each special is at most one record
-    // (it fits TS_DEDUP_MAX), whose key k_sp_drop sets to 0xFFFFFFFF, so that it sorts past the entries.
-    const uint64_t nrec = ne;
-    if (c->sp_S && c->sp_M) {
-        k_sp_drop<<<sx_grid(nrec), SX_T, 0, c->st>>>((uint32_t *)k0, nrec, c->d_sp_pieces, (uint32_t)c->sp_M, ctl + 8);
-        HIPCHK(hipGetLastError());
-        if ((r = ts_read_ctl(c, ctl, hc))) return r;
-        if (hc[8] > c->sp_S || hc[8] > nrec) return fail(BPE_GPU_EINTERNAL, "train_split: more special records than specials");
-        ne = nrec - hc[8];
-    }
-    size_t tb = 0, tb2 = 0;
-    HIPCHK(rocprim::radix_sort_pairs(nullptr, tb, (uint32_t *)k0, (uint32_t *)k1, (uint32_t *)v0, (uint32_t *)v1, nrec, 0, 32, c->st));
-    HIPCHK(rocprim::exclusive_scan(nullptr, tb2, (uint32_t *)elen, (uint32_t *)eoff, 0u, ne + 1, rocprim::plus<uint32_t>(), c->st));
-    tb = std::max(tb, tb2);
-    if ((r = dscratch(c, 26, tb, &tmp))) return r;
-    HIPCHK(rocprim::radix_sort_pairs(tmp, tb, (uint32_t *)k0, (uint32_t *)k1, (uint32_t *)v0, (uint32_t *)v1, nrec, 0, 32, c->st));
-    k_ts_entries<<<(uint32_t)((ne + TS_T) / TS_T), TS_T, 0, c->st>>>(off, (const uint32_t *)k1, ne, (uint64_t *)est, (uint32_t *)elen);
-    HIPCHK(hipGetLastError());
-    HIPCHK(rocprim::exclusive_scan(tmp, tb, (uint32_t *)elen, (uint32_t *)eoff, 0u, ne + 1, rocprim::plus<uint32_t>(), c->st));
-    uint32_t total = 0;
-    HIPCHK(hipMemcpyAsync(&total, (uint32_t *)eoff + ne, 4, hipMemcpyDeviceToHost, c->st));
-    if ((r = ts_read_ctl(c, ctl, hc))) return r;
-    if (hc[TSC_APPEND] != nrec) return fail(BPE_GPU_EINTERNAL, "train_split: entry records do not match their count");
-    if (total < ne || total > c->n0) return fail(BPE_GPU_EINTERNAL, "train_split: entry bytes out of range");
-    *E = ne;
-    *T = total;
-    return 0;
-}
-
-int bpe_gpu_train_split(bpe_gpu_ctx *c, long max_merges, size_t *n_merges) {
-    if (!c || !n_merges) return BPE_GPU_EINVAL;
-    if (!c->loaded) return fail(BPE_GPU_ESTATE, "train_split before load");
-    if (!c->split_ready) return fail(BPE_GPU_ESTATE, "train_split: no split of the loaded bytes");
-    HIPCHK(hipSetDevice(c->dev));
-    c->ts_ready = false;
-    c->ts_merges.clear();
-    uint64_t cap = engine_merge_cap();
-    bool own_cap = true;
-    if (max_merges >= 0 && (uint64_t)max_merges <= cap) {
-        cap = (uint64_t)max_merges;
-        own_cap = false;
-    }
-    int r;
-    void *p;
-    if ((r = dscratch(c, 18, 16 * 4, &p))) return r;
-    uint32_t *ctl = (uint32_t *)p;
-    uint32_t hc[16];
-    uint64_t E = 0, T = 0, nlong = 0, slots = 0;
-    if (c->split_n && (r = ts_piece_table(c, ctl, &E, &T, &nlong, &slots))) return r;
-    const uint64_t T0 = T;
-    uint64_t stop = 0;
-    // Stage B: tok / ent ping-pong (27-30), keep and its scan (31, 32), run heads and their scan (33, 34)
-    uint32_t *tok[2] = {}, *ent[2] = {}, *keep = nullptr, *pos = nullptr, *hv = nullptr, *rs = nullptr;
-    void *tmp = nullptr;
-    size_t tb = 0;
-    if (T) {
-        void *q[8];
-        for (int k = 0; k < 8; k++)
-            if ((r = dscratch(c, 27 + k, (T + 1) * 4, &q[k]))) return r;
-        tok[0] = (uint32_t *)q[0], tok[1] = (uint32_t *)q[1], ent[0] = (uint32_t *)q[2], ent[1] = (uint32_t *)q[3];
-        keep = (uint32_t *)q[4], pos = (uint32_t *)q[5], hv = (uint32_t *)q[6], rs = (uint32_t *)q[7];
-        size_t t1 = 0, t2 = 0;
-        HIPCHK(rocprim::exclusive_scan(nullptr, t1, keep, pos, 0u, T + 1, rocprim::plus<uint32_t>(), c->st));
-        HIPCHK(rocprim::inclusive_scan(nullptr, t2, hv, rs, T, rocprim::maximum<uint32_t>(), c->st));
-        tb = std::max(t1, t2);
-        if ((r = dscratch(c, 26, tb, &tmp))) return r;
-        k_ts_gather<<<ts_grid(T), TS_T, 0, c->st>>>(c->h.bytes, (const uint64_t *)c->dscr[23], (const uint32_t *)c->dscr[25],
-                                                   (uint32_t)E, (uint32_t)T, tok[0], ent[0]);
-        HIPCHK(hipGetLastError());
-    }
-    const uint32_t *ecnt = (const uint32_t *)c->dscr[22];
-    // the pair table starts at 2 T slots or 2^20 and grows like the piece table
-    const uint64_t pmax = std::max<uint64_t>(pow2_at_least(2 * T), 1024) * 16;
-    uint64_t Sp = std::min<uint64_t>(std::max<uint64_t>(pow2_at_least(2 * T), 1024), 1u << 20);
-    void *part;
-    if ((r = dscratch(c, 37, (size_t)TS_GRID * 16, &part))) return r;
-    int cur = 0;
-    for (uint64_t m = 0;; m++) {
-        uint32_t best = 0, a = 0, b = 0;
-        if (T >= 2) {
-            for (;;) {
-                void *pk, *pc;
-                if ((r = dscratch(c, 35, Sp * 8, &pk)) || (r = dscratch(c, 36, Sp * 4, &pc))) return r;
-                HIPCHK(hipMemsetAsync(pk, 0xFF, Sp * 8, c->st));
-                HIPCHK(hipMemsetAsync(pc, 0, Sp * 4, c->st));
-                HIPCHK(hipMemsetAsync(ctl, 0, 16 * 4, c->st));
-                k_tb_count<<<ts_grid(T, 16), TB_CT, 0, c->st>>>(tok[cur], ent[cur], ecnt, (uint32_t)T, (unsigned long long *)pk,
-                                                              (uint32_t *)pc, Sp - 1, ctl);
-                HIPCHK(hipGetLastError());
-                const uint32_t nb = ts_grid(Sp, 4);
-                k_tb_argmax<<<nb, TS_T, 0, c->st>>>((const unsigned long long *)pk, (const uint32_t *)pc, Sp, (unsigned long long *)part);
-                HIPCHK(hipGetLastError());
-                k_tb_argmax2<<<1, TS_T, 0, c->st>>>((const unsigned long long *)part, nb, ctl);
-                HIPCHK(hipGetLastError());
-                if ((r = ts_read_ctl(c, ctl, hc))) return r;
-                if (!hc[TSC_PFULL]) break;
-                if (Sp >= pmax) return fail(BPE_GPU_EINTERNAL, "train_split: the pair table is full at its largest size");
-                Sp *= 4;
-            }
-            best = hc[TSC_CNT], a = hc[TSC_A], b = hc[TSC_B];
-        }
-        if (best <= 1) {  // the reference's rule first: no pair left, or none seen twice
-            stop = 1;
-            break;
-        }
-        if (m == cap) {
-            stop = own_cap ? 3 : 2;
-            break;
-        }
-        const uint32_t z = 256u + (uint32_t)m, g = ts_grid(T, 4);
-        const uint32_t *runs = nullptr;
-        if (a == b) {
-            k_tb_heads<<<g, TS_T, 0, c->st>>>(tok[cur], ent[cur], (uint32_t)T, a, hv);
-            HIPCHK(hipGetLastError());
-            HIPCHK(rocprim::inclusive_scan(tmp, tb, hv, rs, T, rocprim::maximum<uint32_t>(), c->st));
-            runs = rs;
-        }
-        k_tb_flag<<<g, TS_T, 0, c->st>>>(tok[cur], ent[cur], runs, (uint32_t)T, a, b, keep);
-        HIPCHK(hipGetLastError());
-        HIPCHK(rocprim::exclusive_scan(tmp, tb, keep, pos, 0u, T + 1, rocprim::plus<uint32_t>(), c->st));
-        k_tb_scatter<<<g, TS_T, 0, c->st>>>(tok[cur], ent[cur], keep, pos, (uint32_t)T, z, tok[cur ^ 1], ent[cur ^ 1]);
-        HIPCHK(hipGetLastError());
-        uint32_t newT = 0;
-        HIPCHK(hipMemcpyAsync(&newT, pos + T, 4, hipMemcpyDeviceToHost, c->st));
-        HIPCHK(hipStreamSynchronize(c->st));
-        if (newT >= T || newT < E) return fail(BPE_GPU_EINTERNAL, "train_split: a merge removed no token or too many");
-        T = newT;
-        cur ^= 1;
-        c->ts_merges.push_back(a);
-        c->ts_merges.push_back(b);
-    }
-    if (stop == 3)
-        fprintf(stderr,
-                "bpe: training stopped at the engine's merge cap (%llu merges) before the reference's stop rule "
-                "(max count <= 1); pass a merge cap to choose the length\n",
-                (unsigned long long)cap);
-    const uint64_t info[8] = {c->split_n, E, T0, nlong, c->ts_merges.size() / 2, stop, TS_DEDUP_MAX, slots};
-    memcpy(c->ts_info, info, sizeof info);
-    c->ts_ready = true;
-    *n_merges = c->ts_merges.size() / 2;
-    return 0;
-}
-
-int bpe_gpu_fetch_split_merges(bpe_gpu_ctx *c, uint32_t *out, size_t cap, size_t *count) {
-    if (!c || !count) return BPE_GPU_EINVAL;
-    if (!c->loaded || !c->split_ready || !c->ts_ready) return fail(BPE_GPU_ESTATE, "no split merges: train_split first");
-    const size_t k = c->ts_merges.size() / 2;
-    *count = k;
-    if (out) memcpy(out, c->ts_merges.data(), std::min(cap, k) * 8);
-    return 0;
-}
-
-int bpe_gpu_train_split_info(bpe_gpu_ctx *c, uint64_t *out8) {
-    if (!c || !out8) return BPE_GPU_EINVAL;
-    if (!c->loaded || !c->split_ready || !c->ts_ready) return fail(BPE_GPU_ESTATE, "no split training: train_split first");
-    memcpy(out8, c->ts_info, sizeof c->ts_info);
-    return 0;
-}
-
-int bpe_gpu_fetch_piece_table(bpe_gpu_ctx *c, uint64_t *start, uint32_t *len, uint32_t *count, size_t cap, size_t *entries) {
-    if (!c || !entries) return BPE_GPU_EINVAL;
-    if (!c->loaded || !c->split_ready || !c->ts_ready) return fail(BPE_GPU_ESTATE, "no piece table: train_split first");
-    HIPCHK(hipSetDevice(c->dev));
-    *entries = (size_t)c->ts_info[1];
-    const size_t k = std::min<size_t>(cap, *entries);
-    int r;
-    if (k && start && (r = d2h_staged(c, start, c->dscr[23], k * 8))) return r;
-    if (k && len && (r = d2h_staged(c, len, c->dscr[24], k * 4))) return r;
-    if (k && count && (r = d2h_staged(c, count, c->dscr[22], k * 4))) return r;
-    return 0;
-}
-
 int bpe_gpu_fetch_doc_offsets(bpe_gpu_ctx *c, uint64_t *out, size_t cap, size_t *count) {
     if (!c || !count) return BPE_GPU_EINVAL;
     if (!c->ids_ready || !c->docs_ready) return fail(BPE_GPU_ESTATE, "no document offsets: encode_docs first");
@@ -4092,12 +3494,11 @@ static int decode_docs_run(bpe_gpu_ctx *c, const uint32_t *ids, size_t len, cons
     int r;
     if ((r = decode_run(c, ids, len, pairs, n_merges, sp, out, cap, out_len))) return r;
     if (!byte_off) return 0;
-    // byte_off[d] = the ids' expansion-length prefix sum (left in scratch slot 3 by bpe_gpu_decode) at id_off[d]
-    void *d_idx, *d_out;
-    if ((r = dscratch(c, 10, (ndocs + 1) * 8, &d_idx)) || (r = dscratch(c, 11, (ndocs + 1) * 8, &d_out))) return r;
+    // byte_off[d] = the ids' expansion-length prefix sum (left in scratch slot DS_DEC_OFF by decode_run) at id_off[d]
+    uint64_t *d_idx, *d_out;
+    if ((r = dscratch(c, DS_DD_IDOFF, (ndocs + 1) * 8, &d_idx)) || (r = dscratch(c, DS_DD_BYTEOFF, (ndocs + 1) * 8, &d_out))) return r;
     HIPCHK(hipMemcpyAsync(d_idx, id_off, (ndocs + 1) * 8, hipMemcpyHostToDevice, c->st));
-    k_ed_pick<<<(uint32_t)((ndocs + 256) / 256), 256, 0, c->st>>>((const uint64_t *)c->dscr[3], (const uint64_t *)d_idx,
-                                                                  ndocs + 1, (uint64_t *)d_out);
+    k_ed_pick<<<(uint32_t)((ndocs + 256) / 256), 256, 0, c->st>>>((const uint64_t *)c->dscr[DS_DEC_OFF], d_idx, ndocs + 1, d_out);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(byte_off, d_out, (ndocs + 1) * 8, hipMemcpyDeviceToHost, c->st));
     HIPCHK(hipStreamSynchronize(c->st));
@@ -4124,4 +3525,5 @@ int bpe_gpu_decode_docs_special(bpe_gpu_ctx *c, const uint32_t *ids, size_t len,
 }
 
 }  // extern "C"
+#include "pieces.hip"
 #include "shard.hip"

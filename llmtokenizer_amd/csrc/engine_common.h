@@ -609,4 +609,64 @@ __host__ __device__ inline uint32_t thread_of(uint64_t c, uint64_t n) {
     return (uint32_t)((c / CHUNK) % NTHR);
 }
 
+// ---- host side: device scratch
+// The grow-only device scratch slots of a context (dscratch): one allocation each, which stays until the context
+// goes.  What lives in a slot, and the function that fills it.
+enum DScr {
+    DS_DEC_IDS,          // decode_run: the ids to decode
+    DS_DEC_PAIRS,        // decode_run: the merge list
+    DS_DEC_ELEN,         // decode_run: expansion length per id
+    DS_DEC_OFF,          // decode_run: byte offset per id [len + 1]; decode_docs_run picks the documents' from it
+    DS_SCAN_TMP,         // rocprim temporary of decode_run's scan and of the window encoders' (ew_run, ed_run)
+    DS_DEC_OUT,          // decode_run: the decoded bytes
+    DS_DEC_ERR,          // decode_run: error words
+    DS_EW_TABLES,        // the window encoder's tables (EwPlan's image): encode, encode_docs, the shard group
+    DS_EW_HALO,          // shard.hip: halo bytes of a shard's neighbours
+    DS_EW_XCHG,          // shard.hip: the ranks' size / head / tail exchange; relist: the byte-pair histograms
+    DS_DD_IDOFF,         // decode_docs_run: the documents' id offsets
+    DS_DD_BYTEOFF,       // decode_docs_run: the documents' byte offsets
+    DS_SPLIT_TABLE,      // split_run: the start table of a table rule
+    DS_SPLIT_MASK,       // split_run: start masks, a bit per byte
+    DS_SPLIT_COUNTS,     // split_run: starts per wave tile and their scan
+    DS_SPLIT_TMP,        // split_run: rocprim temporary of that scan
+    DS_TS_SLOTS,         // ts_piece_table: the piece hash table's keys
+    DS_TS_SLOT_CNT,      // ts_piece_table: ... and counts
+    DS_TS_CTL,           // bpe_gpu_train_split: control words (TSC_*), shared with ts_piece_table
+    DS_TS_KEY0,          // ts_piece_table: entry records before the sort, piece index
+    DS_TS_VAL0,          // ts_piece_table: ... and count
+    DS_TS_KEY1,          // ts_piece_table: sorted piece indices
+    DS_TS_ECNT,          // ts_piece_table: entry counts in start order (TsTable::count; bpe_gpu_fetch_piece_table)
+    DS_TS_ESTART,        // ts_piece_table: entry starts (TsTable::start; bpe_gpu_fetch_piece_table)
+    DS_TS_ELEN,          // ts_piece_table: entry lengths (bpe_gpu_fetch_piece_table)
+    DS_TS_EOFF,          // ts_piece_table: scanned entry lengths (TsTable::off)
+    DS_TS_TMP,           // rocprim temporary shared by ts_piece_table's sort and scan and bpe_gpu_train_split's scans
+    DS_TS_TOK0,          // bpe_gpu_train_split: tokens, ping
+    DS_TS_TOK1,          // ... pong
+    DS_TS_ENT0,          // bpe_gpu_train_split: the tokens' entries, ping
+    DS_TS_ENT1,          // ... pong
+    DS_TS_KEEP,          // bpe_gpu_train_split: rewrite flags
+    DS_TS_POS,           // ... and their scan
+    DS_TS_HEADS,         // bpe_gpu_train_split: run heads of an a == a merge
+    DS_TS_RUNS,          // ... and their scan
+    DS_TS_PAIR_KEYS,     // bpe_gpu_train_split: the pair table's keys
+    DS_TS_PAIR_CNT,      // ... and counts
+    DS_TS_ARGMAX,        // bpe_gpu_train_split: per-block argmax partials
+    DS_SP_SET,           // sp_find: the specials as the device reads them (SpFound::set)
+    DS_SP_COVER,         // sp_find: cover bitmap, a bit per byte (SpFound::cover)
+    DS_SP_LIST,          // sp_find: the match list (SpFound::list)
+    DS_SP_SORTED,        // sp_patch: the match list sorted by start
+    DS_SP_TMP,           // rocprim temporary of sp_patch's sort and of bpe_gpu_encode_split's scan
+    DS_SP_CTL,           // sp_find: control words (SpFound::ctl)
+    DS_SP_FIRST_ID,      // bpe_gpu_encode_split: first id of every special piece
+    DS_SP_REMOVED,       // bpe_gpu_encode_split: ids removed per special piece
+    DS_SP_REMOVED_SCAN,  // ... and their scan
+    DS_SP_DEC_BYTES,     // decode_run: the specials' bytes
+    DS_SP_DEC_OFF,       // decode_run: ... and offsets
+    DS_CL_CHAINS,        // mark_cl100k: the wave tiles' chain effects and their scan
+    DS_CL_TMP,           // mark_cl100k: rocprim temporary of that scan
+    DS_COUNT
+};
+// bpe_gpu_train_split takes its eight token-sized arrays as one run of slots
+static_assert(DS_TS_RUNS - DS_TS_TOK0 == 7, "the slots DS_TS_TOK0 .. DS_TS_RUNS are contiguous");
+
 }  // namespace bpeamd

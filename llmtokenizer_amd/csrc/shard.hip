@@ -806,9 +806,9 @@ int group_encode_window_ranks(bpe_gpu_group *g, const uint32_t *pairs, size_t n_
     if (!P.ok || (g->p2p && count + 1 > g->hp.c0)) return 0;  // (the same on every rank)
     int r;
     void *d_img, *xb, *hb;
-    if ((r = dscratch(c, 7, P.words * 4, &d_img))) return r;
+    if ((r = dscratch(c, DS_EW_TABLES, P.words * 4, &d_img))) return r;
     HIPCHK(hipMemcpyAsync(d_img, c->ew_stage.data(), P.words * 4, hipMemcpyHostToDevice, g->st));
-    if ((r = dscratch(c, 9, (count + 1) * 4, &xb))) return r;
+    if ((r = dscratch(c, DS_EW_XCHG, (count + 1) * 4, &xb))) return r;
     uint32_t *x = (uint32_t *)xb;
     HIPCHK(hipMemsetAsync(x, 0, count * 4, g->st));
     const uint64_t n = c->n0;
@@ -847,7 +847,7 @@ int group_encode_window_ranks(bpe_gpu_group *g, const uint32_t *pairs, size_t n_
         while (gpos >= start[k + 1]) k++;
         halo[lav + i] = ((const uint8_t *)&hx[(size_t)k * SLOT + 2])[gpos - start[k]];  // in k's head
     }
-    if ((r = dscratch(c, 8, halo.size(), &hb))) return r;
+    if ((r = dscratch(c, DS_EW_HALO, halo.size(), &hb))) return r;
     HIPCHK(hipMemcpyAsync(hb, halo.data(), halo.size(), hipMemcpyHostToDevice, g->st));
     HIPCHK(hipStreamSynchronize(g->st));  // (halo is a host vector)
     const uint8_t *lh = (const uint8_t *)hb, *rh = lh + lav;
@@ -906,7 +906,7 @@ int group_encode(bpe_gpu_group *g, const uint32_t *pairs, size_t n_merges) {
         const EwPlan P = ew_plan(pairs, n_merges, c0->ew_stage);
         if (P.ok) {
             void *d_img;
-            if ((r = dscratch(c0, 7, P.words * 4, &d_img))) return r;
+            if ((r = dscratch(c0, DS_EW_TABLES, P.words * 4, &d_img))) return r;
             HIPCHK(hipMemcpyAsync(d_img, c0->ew_stage.data(), P.words * 4, hipMemcpyHostToDevice, g->st));
             std::vector<uint64_t> start(K + 1, 0);
             for (uint32_t k = 0; k < K; k++) start[k + 1] = start[k] + g->cs[k]->n0;
@@ -926,7 +926,7 @@ int group_encode(bpe_gpu_group *g, const uint32_t *pairs, size_t n_merges) {
                     const uint32_t lav = (uint32_t)std::min<uint64_t>(EW_HALO_WIDE, start[k]);
                     const uint32_t rav = (uint32_t)std::min<uint64_t>(EW_HALO_WIDE, ntot - start[k + 1]);
                     void *hb;
-                    if ((r = dscratch(c, 8, lav + rav + 16, &hb))) return r;
+                    if ((r = dscratch(c, DS_EW_HALO, lav + rav + 16, &hb))) return r;
                     uint8_t *lh = (uint8_t *)hb, *rh = lh + lav;
                     if ((r = group_copy_bytes(g, start, start[k] - lav, lav, lh))) return r;
                     if ((r = group_copy_bytes(g, start, start[k + 1], rav, rh))) return r;

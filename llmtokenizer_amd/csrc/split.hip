@@ -1,4 +1,4 @@
-// split.hip -- pieces of the resident bytes by a two-table rule or by a preset with a marking kernel of its own; included by engine.hip.
+// split.hip -- pieces of the resident bytes by a two-table rule or by a preset with a marking kernel of its own; included by engine.hip; its host side is pieces.hip.
 //
 // A rule is cls[256] (a class 0..15 per byte value) and brk[16]: a piece
 // starts at byte i > 0 when bit cls[b[i]] of brk[cls[b[i - 1]]] is set, and at
@@ -26,7 +26,7 @@
 //   k_cl_summary, k_split_mark_cl100k  the same pass for BPE_SPLIT_CL100K, whose starts also depend on runs
 //                  of any length: a summary pass, a scan of its per-wave-tile effects and the marking
 //                  pass that takes their result in (described where they are, below);
-//   (rocprim::exclusive_scan of the wave counts, engine.hip)
+//   (rocprim::exclusive_scan of the wave counts, split_run in pieces.hip)
 //   k_split_emit   reads the masks again (n / 8 bytes, not the bytes): a wave
 //                  ranks its starts, stages their positions in LDS and writes
 //                  them as consecutive 8-byte offsets at its scanned base.

@@ -1,4 +1,4 @@
-// train_split.hip -- training on the pieces of the last split; included by engine.hip.
+// train_split.hip -- training on the pieces of the last split; included by engine.hip; its host side is pieces.hip.
 //
 // The corpus is the multiset of pieces (split.hip's offsets over the resident
 // bytes): a pair is counted only inside one piece and a merge is applied inside

@@ -9,6 +9,7 @@
  * bpe_special_gpu.c.
  */
 #include "../../include/bpe_ex.h"
+#include "bpe_split_presets.h"
 
 #include <stdio.h>
 #include <string.h>
@@ -121,8 +122,7 @@ int bpe_split_offsets_host_special(int preset, const uint8_t *cls, const uint16_
         if (!cls || !brk) return BPE_GPU_EINVAL;
         for (int b = 0; b < 256; b++)
             if (cls[b] > 15) return BPE_GPU_EINVAL;
-    } else if (preset != BPE_SPLIT_LINES && preset != BPE_SPLIT_WORDS && preset != BPE_SPLIT_GPT2 &&
-               preset != BPE_SPLIT_GPT2_UNICODE && preset != BPE_SPLIT_CL100K) {
+    } else if (!split_preset_find(preset)) {
         return BPE_GPU_EINVAL;
     }
     int rc = bpe_specials_check(sp, NULL, 0);

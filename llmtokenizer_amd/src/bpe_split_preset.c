@@ -5,6 +5,7 @@
  * bpe_gpu_split_preset, on the bodies bpe_encode_split and bpe_train_split run.
  */
 #include "bpe_internal.h"
+#include "bpe_split_presets.h"
 #include "../csrc/unicode_classes.h"
 
 enum { C_P = 0, C_L = 1, C_N = 2, C_S = 3, C_W = 4 }; /* the classes of BPE_SPLIT_WORDS and BPE_SPLIT_GPT2 */
@@ -245,9 +246,7 @@ static int starts_words(const uint8_t *b, size_t i)
 int bpe_split_offsets_host(int preset, const uint8_t *bytes, size_t n, uint64_t *out, size_t cap, size_t *count)
 {
     if ((!bytes && n) || !count) return BPE_GPU_EINVAL;
-    if (preset != BPE_SPLIT_LINES && preset != BPE_SPLIT_WORDS && preset != BPE_SPLIT_GPT2 && preset != BPE_SPLIT_GPT2_UNICODE &&
-        preset != BPE_SPLIT_CL100K)
-        return BPE_GPU_EINVAL;
+    if (!split_preset_find(preset)) return BPE_GPU_EINVAL;
     size_t k = 0;
     if (preset == BPE_SPLIT_CL100K) {
         starts_cl100k(bytes, n, out, cap, &k);
