@@ -30,6 +30,11 @@ COBJ_SP := $(patsubst $(PKG)/src/%.c,$(BUILD)/%.o,$(CSRC_SP))
 CSRC_SPECIAL := $(PKG)/src/bpe_special.c
 CSRC_SPECIAL_GPU := $(PKG)/src/bpe_special_gpu.c
 COBJ_SPECIAL := $(patsubst $(PKG)/src/%.c,$(BUILD)/%.o,$(CSRC_SPECIAL) $(CSRC_SPECIAL_GPU))
+# vocabularies: src/bpe_vocab.c is host code alone (the check and the two tables; no engine call, so
+# tests/asan_vocab needs no model), src/bpe_vocab_gpu.c the entry points over bpe_gpu_map_ids & co.
+CSRC_VOCAB := $(PKG)/src/bpe_vocab.c
+CSRC_VOCAB_GPU := $(PKG)/src/bpe_vocab_gpu.c
+COBJ_VOCAB := $(patsubst $(PKG)/src/%.c,$(BUILD)/%.o,$(CSRC_VOCAB) $(CSRC_VOCAB_GPU))
 HIPDEPS := $(wildcard $(PKG)/csrc/*.hip $(PKG)/csrc/*.h) $(PKG)/src/bpe_split_presets.h include/bpe_gpu.h
 
 all: $(PKG)/libbpe_amd.so tools/bpe_main oracle
@@ -43,7 +48,7 @@ $(BUILD)/engine.o: $(HIPDEPS) | $(BUILD)
 $(BUILD)/%.o: $(PKG)/src/%.c $(wildcard include/*.h $(PKG)/src/*.h $(PKG)/csrc/unicode_classes.h) | $(BUILD)
 	$(CC) $(CFLAGS) -c $< -o $@
 
-$(PKG)/libbpe_amd.so: $(BUILD)/engine.o $(COBJ) $(COBJ_GPU) $(COBJ_TS) $(COBJ_SP) $(COBJ_SPECIAL)
+$(PKG)/libbpe_amd.so: $(BUILD)/engine.o $(COBJ) $(COBJ_GPU) $(COBJ_TS) $(COBJ_SP) $(COBJ_SPECIAL) $(COBJ_VOCAB)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -lm -ldl -lpthread
 
 tools/bpe_main: tools/bpe_main.c $(PKG)/libbpe_amd.so
@@ -128,3 +133,12 @@ tests/asan_split_cl100k/asan_split_cl100k: tests/asan_split_cl100k/asan_split_cl
 
 asan-split-cl100k: tests/asan_split_cl100k/asan_split_cl100k
 .PHONY: asan-split-cl100k
+
+# the vocabularies' host code (src/bpe_vocab.c: bpe_vocab_check and bpe_vocab_tables) the same way, in a stand-alone
+# program that calls no engine function (tests/asan_vocab/asan_vocab.c); run by tests/test_asan_vocab.py
+tests/asan_vocab/asan_vocab: tests/asan_vocab/asan_vocab.c $(CSRC_VOCAB) $(wildcard include/*.h)
+	$(CC) -O1 -g -std=c11 -D_GNU_SOURCE -fno-omit-frame-pointer -fsanitize=address,undefined \
+	    -fno-sanitize-recover=undefined -Iinclude -o $@ tests/asan_vocab/asan_vocab.c $(CSRC_VOCAB) -lm
+
+asan-vocab: tests/asan_vocab/asan_vocab
+.PHONY: asan-vocab

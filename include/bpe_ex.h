@@ -122,6 +122,28 @@ dyn_arr_t *bpe_train_split_special(const uint8_t *bytes, size_t n, int preset, c
 char *bpe_decode_docs_special(const uint32_t *ids, size_t len, const uint64_t *id_off, size_t ndocs, dyn_arr_t *pair_arr,
                               const bpe_gpu_specials *specials, int device, size_t *out_len, uint64_t **byte_off);
 
+/* Vocabularies (bpe_gpu.h, "Vocabularies").  bpe_vocab_check: 0 when the ids of `vocab` are pairwise distinct
+ * across its three arrays and below BPE_VOCAB_ID_LIMIT, vocab->n_merges == n_merges, it has at most
+ * BPE_GPU_SPECIAL_MAX_COUNT specials and, unless pairs is NULL, both parts of merge r (pairs[2 r], pairs[2 r + 1])
+ * are below 256 + r; else BPE_GPU_EINVAL and, unless msg is NULL, a message in msg[0 .. msg_cap) that names
+ * the offender ("byte 0x21 and merge 7 share the id 5").  No GPU. */
+int bpe_vocab_check(const bpe_gpu_vocab *vocab, const uint32_t *pairs, size_t n_merges, char *msg, size_t msg_cap);
+/* The two tables of a vocabulary bpe_vocab_check accepts (else its code): fwd[k] = the vocabulary id of internal
+ * id k, *n_fwd = 256 + n_merges + n_specials entries; inv[id] = the internal id of vocabulary id `id` or
+ * 0xFFFFFFFF for a hole, *n_inv = the largest id + 1 entries.  Two-phase: either array may be NULL, at most
+ * fwd_cap / inv_cap entries are written.  No GPU. */
+int bpe_vocab_tables(const bpe_gpu_vocab *vocab, uint32_t *fwd, size_t fwd_cap, uint32_t *inv, size_t inv_cap,
+                     size_t *n_fwd, size_t *n_inv);
+/* bpe_encode_split_special whose ids are the vocabulary's (bpe_gpu_map_ids after the encode); specials may be
+ * NULL when vocab->n_specials == 0.  Results and ownership as bpe_encode_split. */
+uint32_t *bpe_encode_split_vocab(const uint8_t *bytes, size_t n, int preset, const uint8_t *cls, const uint16_t *brk,
+                                 const bpe_gpu_specials *specials, dyn_arr_t *pair_arr, const bpe_gpu_vocab *vocab,
+                                 int device, size_t *len, uint64_t **id_off, uint64_t **byte_off, size_t *ndocs);
+/* bpe_decode_docs_special over vocabulary ids (bpe_gpu_decode_docs_vocab) */
+char *bpe_decode_docs_vocab(const uint32_t *ids, size_t len, const uint64_t *id_off, size_t ndocs, dyn_arr_t *pair_arr,
+                            const bpe_gpu_specials *specials, const bpe_gpu_vocab *vocab, int device, size_t *out_len,
+                            uint64_t **byte_off);
+
 /* statistics of the last compress/compress_ex/bpe_train_bytes/bpe_encode_bytes/bpe_encode_docs/bpe_encode_split(_preset) */
 int bpe_last_stats(bpe_gpu_stats *out);
 

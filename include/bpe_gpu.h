@@ -502,6 +502,49 @@ int bpe_gpu_decode_docs_special(bpe_gpu_ctx *ctx, const uint32_t *ids, size_t le
                                 const bpe_gpu_specials *specials, uint8_t *out, size_t cap, size_t *out_len,
                                 uint64_t *byte_off);
 
+/* ------------------------------------------------------------------------
+ * Vocabularies: a tokenizer's own numbering of the tokens.  The engine's ids
+ * are byte b = b, merge r = 256 + r, special j = 256 + n_merges + j (the
+ * internal ids).  A vocabulary gives each of them another id: pairwise distinct
+ * over the three arrays, each below BPE_VOCAB_ID_LIMIT (2^24, the engine's own
+ * merge cap; it bounds the inverse table at 64 MB), holes allowed.  The merge
+ * list it belongs to names, for merge r, only ids below 256 + r: replaying such
+ * a list in rank order (what the encoders do) is the usual lowest-rank-first BPE
+ * (bpe_ex.h bpe_vocab_check).
+ *
+ * bpe_gpu_map_ids rewrites the resident ids in place, ids[i] = fwd[ids[i]]
+ * (k_ids_map); the offsets of a document batch do not move.  The context
+ * remembers that its ids are vocabulary ids: the mark goes when the ids go
+ * (any load, synth, trim, encode or training that replaces them), and while it
+ * stands a second bpe_gpu_map_ids is BPE_GPU_ESTATE, as is any call that would
+ * read the resident ids as internal ones.  bpe_gpu_decode_docs_vocab turns the
+ * caller's ids back on the device first (k_ids_unmap); an id past the inverse
+ * table or in a hole is an unknown token id, BPE_GPU_EDATA.
+ * ---------------------------------------------------------------------- */
+#define BPE_VOCAB_ID_LIMIT (1u << 24)
+typedef struct {
+    const uint32_t *byte_id;    /* 256: vocabulary id of byte b            */
+    const uint32_t *merge_id;   /* n_merges: vocabulary id of merge r      */
+    const uint32_t *special_id; /* n_specials: vocabulary id of special j  */
+    size_t n_merges, n_specials;
+} bpe_gpu_vocab;
+/* Rewrite the ids of the last bpe_gpu_encode / _encode_docs / _encode_split (or training) to vocabulary ids;
+   bpe_gpu_fetch_ids / _fetch_ids_range / _ids_checksum / _fetch_doc_offsets serve them afterwards.
+   BPE_GPU_ESTATE without resident ids or when they are mapped already; BPE_GPU_EINVAL for a vocabulary
+   bpe_vocab_check refuses or whose merge count is not the encode's; BPE_GPU_EINTERNAL should an id lie at or
+   above 256 + n_merges + n_specials (it is compared before the lookup and never used as an index; the ids
+   are dropped then). */
+int bpe_gpu_map_ids(bpe_gpu_ctx *ctx, const bpe_gpu_vocab *vocab);
+/* out4 = {ids one thread moves per step, ids per workgroup step, ids per grid step, 0} of k_ids_map and
+   k_ids_unmap (pure function, no GPU; for the tests) */
+int bpe_gpu_map_info(uint64_t *out4);
+/* bpe_gpu_decode_docs_special over vocabulary ids (specials may be NULL when vocab->n_specials == 0; the two
+   counts must agree, as must vocab->n_merges and n_merges) */
+int bpe_gpu_decode_docs_vocab(bpe_gpu_ctx *ctx, const uint32_t *ids, size_t len, const uint64_t *id_off, size_t ndocs,
+                              const uint32_t *pairs, size_t n_merges, const bpe_gpu_specials *specials,
+                              const bpe_gpu_vocab *vocab, uint8_t *out, size_t cap, size_t *out_len,
+                              uint64_t *byte_off);
+
 int bpe_gpu_get_stats(bpe_gpu_ctx *ctx, bpe_gpu_stats *st);
 
 /* Position-keyed checksum of the ids of the last train / encode, computed in

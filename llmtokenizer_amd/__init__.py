@@ -7,3 +7,4 @@ this package is its Python binding plus the synthetic-corpus generator.
 from .api import (BpeError, Engine, compress, decompress, device_count, dump_pairs, encode,  # noqa: F401
                   last_stats, read_pairs, train_bytes)
 from .synth import synth_bytes  # noqa: F401
+from .vocab import Tokenizer, Vocab  # noqa: F401

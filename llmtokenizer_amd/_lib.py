@@ -50,12 +50,21 @@ EXPORTS = [
     "bpe_gpu_split_special", "bpe_gpu_split_special_info", "bpe_gpu_fetch_special_pieces", "bpe_gpu_decode_docs_special",
     "bpe_specials_check", "bpe_split_offsets_host_special", "bpe_encode_split_special", "bpe_train_split_special",
     "bpe_decode_docs_special",
+    # bpe_gpu.h / bpe_ex.h: vocabularies
+    "bpe_gpu_map_ids", "bpe_gpu_map_info", "bpe_gpu_decode_docs_vocab", "bpe_vocab_check", "bpe_vocab_tables",
+    "bpe_encode_split_vocab", "bpe_decode_docs_vocab",
 ]
 
 
 class Specials(ctypes.Structure):
     """bpe_gpu.h bpe_gpu_specials"""
     _fields_ = [("bytes", ctypes.c_void_p), ("len", ctypes.c_void_p), ("count", ctypes.c_size_t)]
+
+
+class VocabIds(ctypes.Structure):
+    """bpe_gpu.h bpe_gpu_vocab"""
+    _fields_ = [("byte_id", ctypes.c_void_p), ("merge_id", ctypes.c_void_p), ("special_id", ctypes.c_void_p),
+                ("n_merges", ctypes.c_size_t), ("n_specials", ctypes.c_size_t)]
 
 
 class GpuStats(ctypes.Structure):
@@ -242,6 +251,19 @@ def load():
     L.bpe_decode_docs_special.argtypes = [vp, sz, vp, sz, ctypes.POINTER(DynArr), spp, ctypes.c_int, ctypes.POINTER(sz),
                                           ctypes.POINTER(u64p)]
     L.bpe_decode_docs_special.restype = ctypes.c_void_p
+    vop = ctypes.POINTER(VocabIds)
+    L.bpe_gpu_map_ids.argtypes = [vp, vop]
+    L.bpe_gpu_map_info.argtypes = [vp]
+    L.bpe_gpu_decode_docs_vocab.argtypes = [vp, vp, sz, vp, sz, vp, sz, spp, vop, vp, sz, ctypes.POINTER(sz), vp]
+    L.bpe_vocab_check.argtypes = [vop, vp, sz, ctypes.c_char_p, sz]
+    L.bpe_vocab_tables.argtypes = [vop, vp, sz, vp, sz, ctypes.POINTER(sz), ctypes.POINTER(sz)]
+    L.bpe_encode_split_vocab.argtypes = [vp, sz, ctypes.c_int, vp, vp, spp, ctypes.POINTER(DynArr), vop, ctypes.c_int,
+                                         ctypes.POINTER(sz), ctypes.POINTER(u64p), ctypes.POINTER(u64p),
+                                         ctypes.POINTER(sz)]
+    L.bpe_encode_split_vocab.restype = u32p
+    L.bpe_decode_docs_vocab.argtypes = [vp, sz, vp, sz, ctypes.POINTER(DynArr), spp, vop, ctypes.c_int,
+                                        ctypes.POINTER(sz), ctypes.POINTER(u64p)]
+    L.bpe_decode_docs_vocab.restype = ctypes.c_void_p
     L.bpe_release_engines.argtypes = []
     L.bpe_release_engines.restype = None
     _LIB = L

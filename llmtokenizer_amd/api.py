@@ -303,6 +303,14 @@ def split_info():
     return {"tile": int(out[0]), "grid_bytes": int(out[1])}
 
 
+def map_info():
+    """{"thread", "workgroup", "grid"}: ids one thread of the id-mapping kernels moves per step, ids per
+    workgroup step and ids per grid step (bpe_gpu_map_info; for the tests)"""
+    out = np.zeros(4, dtype=np.uint64)
+    _lib.check(_lib.load().bpe_gpu_map_info(out.ctypes.data_as(ctypes.c_void_p)), "map_info")
+    return {"thread": int(out[0]), "workgroup": int(out[1]), "grid": int(out[2])}
+
+
 def _rule_tables(rule):
     cls, brk = split_rule(rule) if isinstance(rule, str) else rule
     cls = np.ascontiguousarray(cls, dtype=np.uint8).reshape(-1)
@@ -626,9 +634,16 @@ class Engine:
         _lib.check(self.L.bpe_gpu_docs_info(self.ctx, out.ctypes.data_as(ctypes.c_void_p)), "docs_info")
         return {k: int(out[i]) for i, k in enumerate(self.DOCS_INFO)}
 
-    def decode_docs(self, ids, offsets, merges, specials=None):
+    def map_ids(self, vocab):
+        """rewrite the resident ids of the last encode in place to the ids of vocab (a vocab.Vocab):
+        ids(), ids_checksum() and doc_offsets() serve them afterwards, the offsets unchanged
+        (bpe_gpu_map_ids).  A second map_ids, or one without ids, raises BpeError (BPE_GPU_ESTATE)."""
+        _lib.check(self.L.bpe_gpu_map_ids(self.ctx, vocab.c_vocab().ref), "map_ids")
+
+    def decode_docs(self, ids, offsets, merges, specials=None, vocab=None):
         """(bytes, byte offsets) of ids held as documents (bpe_gpu_decode_docs); with specials (see split) the
-        id 256 + len(merges) + j is specials[j] (bpe_gpu_decode_docs_special)"""
+        id 256 + len(merges) + j is specials[j] (bpe_gpu_decode_docs_special); with vocab (a vocab.Vocab
+        over the same merges and specials) the ids are the vocabulary's (bpe_gpu_decode_docs_vocab)"""
         ids = np.ascontiguousarray(ids, dtype=np.uint32)
         off = _doc_offsets(offsets)
         if off.size < 1:
@@ -643,6 +658,10 @@ class Engine:
             check_specials(specials)
             sp = _Specials(specials)
             fn, args = self.L.bpe_gpu_decode_docs_special, args + (sp.ref,)
+        if vocab is not None:
+            cv = vocab.c_vocab()
+            fn = self.L.bpe_gpu_decode_docs_vocab
+            args = (args if specials is not None else args + (None,)) + (cv.ref,)
         _lib.check(fn(*args, None, 0, ctypes.byref(n), None), "decode_docs")
         out = np.zeros(max(n.value, 1), dtype=np.uint8)
         bo = np.zeros(off.size, dtype=np.uint64)

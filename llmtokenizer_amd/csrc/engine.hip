@@ -29,9 +29,14 @@
 #include "split.hip"
 #include "train_split.hip"
 #include "special.hip"
+#include "vocab.hip"
 
 // (bpe_ex.h, src/bpe_special.c: the host definition of a valid set)
 extern "C" int bpe_specials_check(const bpe_gpu_specials *specials, char *msg, size_t msg_cap);
+// (bpe_ex.h, src/bpe_vocab.c: the host definition of a valid vocabulary and its two tables)
+extern "C" int bpe_vocab_check(const bpe_gpu_vocab *vocab, const uint32_t *pairs, size_t n_merges, char *msg, size_t msg_cap);
+extern "C" int bpe_vocab_tables(const bpe_gpu_vocab *vocab, uint32_t *fwd, size_t fwd_cap, uint32_t *inv, size_t inv_cap,
+                                size_t *n_fwd, size_t *n_inv);
 
 using namespace bpeamd;
 
@@ -296,6 +301,7 @@ struct bpe_gpu_ctx {
     bool loaded = false;
     bool ids_ready = false;
     uint64_t ids_len = 0;
+    bool ids_mapped = false;  // bpe_gpu_map_ids made them vocabulary ids; goes with the ids (free_train)
     // the last bpe_gpu_encode_docs: id offsets (device, [docs_n + 1]) and bpe_gpu_docs_info's counters
     bool docs_ready = false;
     uint64_t docs_n = 0;
@@ -488,6 +494,7 @@ void free_train(bpe_gpu_ctx *c, bool release = false) {
         if (real_graph(g)) (void)hipGraphExecDestroy(g);
     c->retired.clear();
     c->ids_ready = false;
+    c->ids_mapped = false;
     c->docs_ready = false;
 }
 
@@ -2959,11 +2966,19 @@ void dec_elen_host(const uint32_t *pairs, uint32_t nm, uint64_t *elen) {
     }
 }
 
+// workgroups of k_ids_map / k_ids_unmap for len ids (vocab.hip)
+static uint32_t vm_grid(uint64_t len) {
+    const uint64_t step = (uint64_t)VM_T * VM_PER;
+    return (uint32_t)std::min<uint64_t>(std::max<uint64_t>((len + step - 1) / step, 1), VM_GRID);
+}
+
 // The body of bpe_gpu_decode (sp == nullptr or an empty set: its launches and nothing else) and of
 // bpe_gpu_decode_docs_special: the ids V0 .. V0 + S - 1 past the merge list's are the (checked) specials, whose
-// lengths follow the merge list's in elen and whose bytes k_sp_dec_expand copies.
+// lengths follow the merge list's in elen and whose bytes k_sp_dec_expand copies.  With a vocabulary (checked by
+// the caller) the uploaded ids are its ids and are turned into internal ones first (k_ids_unmap).
 static int decode_run(bpe_gpu_ctx *c, const uint32_t *ids, size_t len, const uint32_t *pairs, size_t n_merges,
-                      const bpe_gpu_specials *sp, uint8_t *out, size_t cap, size_t *out_len) {
+                      const bpe_gpu_specials *sp, uint8_t *out, size_t cap, size_t *out_len,
+                      const bpe_gpu_vocab *vocab = nullptr) {
     if (!c || !out_len || (!ids && len) || (!pairs && n_merges)) return BPE_GPU_EINVAL;
     if (n_merges > 0xFFFFFEFFull) return fail(BPE_GPU_ERANGE, "merge list too long");
     const uint32_t S = sp ? (uint32_t)sp->count : 0u;
@@ -2996,6 +3011,18 @@ static int decode_run(bpe_gpu_ctx *c, const uint32_t *ids, size_t len, const uin
     HIPCHK(hipMemsetAsync(d_err, 0, 8, c->st));
     if (len) HIPCHK(hipMemcpyAsync(d_ids, ids, len * 4, hipMemcpyHostToDevice, c->st));
     if (n_merges) HIPCHK(hipMemcpyAsync(d_pairs, pairs, n_merges * 8, hipMemcpyHostToDevice, c->st));
+    std::vector<uint32_t> inv;  // (lives until the synchronisation below)
+    if (vocab && len) {
+        size_t nf = 0, ni = 0;
+        if ((r = bpe_vocab_tables(vocab, nullptr, 0, nullptr, 0, &nf, &ni))) return fail(r, "decode: the vocabulary's tables");
+        inv.resize(ni);
+        if ((r = bpe_vocab_tables(vocab, nullptr, 0, inv.data(), ni, &nf, &ni))) return fail(r, "decode: the vocabulary's tables");
+        uint32_t *d_inv;
+        if ((r = dscratch(c, DS_VOC_INV, ni * 4, &d_inv))) return r;
+        HIPCHK(hipMemcpyAsync(d_inv, inv.data(), ni * 4, hipMemcpyHostToDevice, c->st));
+        k_ids_unmap<<<vm_grid(len), VM_T, 0, c->st>>>(d_ids, len, d_inv, (uint32_t)ni, d_err);  // (bit 0: unknown token id)
+        HIPCHK(hipGetLastError());
+    }
     k_dec_elen<<<1, 1024, 0, c->st>>>(d_pairs, (uint32_t)n_merges, d_elen, DEC_MAX_PASSES, d_err + 1);
     HIPCHK(hipGetLastError());
     {
@@ -3486,13 +3513,13 @@ int bpe_gpu_docs_info(bpe_gpu_ctx *c, uint64_t *out8) {
 // the body of bpe_gpu_decode_docs (sp == nullptr) and of bpe_gpu_decode_docs_special
 static int decode_docs_run(bpe_gpu_ctx *c, const uint32_t *ids, size_t len, const uint64_t *id_off, size_t ndocs,
                            const uint32_t *pairs, size_t n_merges, const bpe_gpu_specials *sp, uint8_t *out, size_t cap,
-                           size_t *out_len, uint64_t *byte_off) {
+                           size_t *out_len, uint64_t *byte_off, const bpe_gpu_vocab *vocab = nullptr) {
     if (!c || !out_len || !id_off || (!ids && len) || (!pairs && n_merges)) return BPE_GPU_EINVAL;
     if (id_off[0] != 0 || id_off[ndocs] != len) return fail(BPE_GPU_EINVAL, "decode_docs: offsets must run from 0 to len");
     for (size_t d = 0; d < ndocs; d++)
         if (id_off[d] > id_off[d + 1]) return fail(BPE_GPU_EINVAL, "decode_docs: offsets decrease");
     int r;
-    if ((r = decode_run(c, ids, len, pairs, n_merges, sp, out, cap, out_len))) return r;
+    if ((r = decode_run(c, ids, len, pairs, n_merges, sp, out, cap, out_len, vocab))) return r;
     if (!byte_off) return 0;
     // byte_off[d] = the ids' expansion-length prefix sum (left in scratch slot DS_DEC_OFF by decode_run) at id_off[d]
     uint64_t *d_idx, *d_out;
@@ -3522,6 +3549,69 @@ int bpe_gpu_decode_docs_special(bpe_gpu_ctx *c, const uint32_t *ids, size_t len,
         return decode_run(c, ids, len, pairs, n_merges, specials, out, cap, out_len);
     }
     return decode_docs_run(c, ids, len, id_off, ndocs, pairs, n_merges, specials, out, cap, out_len, byte_off);
+}
+
+// ------------------------------------------------ vocabulary ids (vocab.hip)
+
+int bpe_gpu_map_info(uint64_t *out4) {
+    if (!out4) return BPE_GPU_EINVAL;
+    out4[0] = VM_PER;
+    out4[1] = (uint64_t)VM_PER * VM_T;
+    out4[2] = (uint64_t)VM_PER * VM_T * VM_GRID;
+    out4[3] = 0;
+    return 0;
+}
+
+int bpe_gpu_map_ids(bpe_gpu_ctx *c, const bpe_gpu_vocab *vocab) {
+    if (!c || !vocab) return BPE_GPU_EINVAL;
+    if (!c->ids_ready) return fail(BPE_GPU_ESTATE, "map_ids: no ids: encode first");
+    if (c->ids_mapped) return fail(BPE_GPU_ESTATE, "map_ids: the resident ids are vocabulary ids already");
+    char msg[400];
+    int r;
+    if ((r = bpe_vocab_check(vocab, nullptr, vocab->n_merges, msg, sizeof msg))) return fail(r, r == BPE_GPU_EINVAL ? msg : "map_ids: out of memory");
+    if (c->ids_len && vocab->n_merges != c->stats.merges) {
+        snprintf(msg, sizeof msg, "map_ids: the vocabulary numbers %zu merges, the ids were made with %llu", vocab->n_merges,
+                 (unsigned long long)c->stats.merges);
+        return fail(BPE_GPU_EINVAL, msg);
+    }
+    c->ids_mapped = true;
+    if (!c->ids_len) return 0;
+    HIPCHK(hipSetDevice(c->dev));
+    size_t nf = 0, ni = 0;
+    std::vector<uint32_t> fwd(256 + vocab->n_merges + vocab->n_specials);
+    if ((r = bpe_vocab_tables(vocab, fwd.data(), fwd.size(), nullptr, 0, &nf, &ni))) return fail(r, "map_ids: the vocabulary's tables");
+    uint32_t *d_fwd, *d_err, err = 0;
+    if ((r = dscratch(c, DS_VOC_FWD, nf * 4, &d_fwd)) || (r = dscratch(c, DS_VOC_ERR, 64, &d_err))) return r;
+    HIPCHK(hipMemcpyAsync(d_fwd, fwd.data(), nf * 4, hipMemcpyHostToDevice, c->st));
+    HIPCHK(hipMemsetAsync(d_err, 0, 4, c->st));
+    k_ids_map<<<vm_grid(c->ids_len), VM_T, 0, c->st>>>(c->h.ids_out, c->ids_len, d_fwd, (uint32_t)nf, d_err);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipStreamSynchronize(c->st));
+    if (err) {  // (the ids are half rewritten: they are gone)
+        c->ids_ready = false;
+        c->ids_mapped = false;
+        c->docs_ready = false;
+        return fail(BPE_GPU_EINTERNAL, "map_ids: a resident id at or above 256 + merges + specials of the vocabulary");
+    }
+    return 0;
+}
+
+int bpe_gpu_decode_docs_vocab(bpe_gpu_ctx *c, const uint32_t *ids, size_t len, const uint64_t *id_off, size_t ndocs,
+                              const uint32_t *pairs, size_t n_merges, const bpe_gpu_specials *specials,
+                              const bpe_gpu_vocab *vocab, uint8_t *out, size_t cap, size_t *out_len, uint64_t *byte_off) {
+    if (!c || !vocab || (!pairs && n_merges)) return BPE_GPU_EINVAL;
+    char msg[400];
+    int r;
+    if (bpe_specials_check(specials, msg, sizeof msg)) return fail(BPE_GPU_EINVAL, msg);
+    if ((r = bpe_vocab_check(vocab, pairs, n_merges, msg, sizeof msg))) return fail(r, r == BPE_GPU_EINVAL ? msg : "decode_docs_vocab: out of memory");
+    if ((specials ? specials->count : 0) != vocab->n_specials)
+        return fail(BPE_GPU_EINVAL, "decode_docs_vocab: the vocabulary's special count is not the set's");
+    if (!id_off) {  // one flat sequence
+        if (ndocs) return fail(BPE_GPU_EINVAL, "decode_docs_vocab: documents without offsets");
+        return decode_run(c, ids, len, pairs, n_merges, specials, out, cap, out_len, vocab);
+    }
+    return decode_docs_run(c, ids, len, id_off, ndocs, pairs, n_merges, specials, out, cap, out_len, byte_off, vocab);
 }
 
 }  // extern "C"

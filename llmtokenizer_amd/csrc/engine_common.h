@@ -664,6 +664,9 @@ enum DScr {
     DS_SP_DEC_OFF,       // decode_run: ... and offsets
     DS_CL_CHAINS,        // mark_cl100k: the wave tiles' chain effects and their scan
     DS_CL_TMP,           // mark_cl100k: rocprim temporary of that scan
+    DS_VOC_FWD,          // bpe_gpu_map_ids: the forward table, internal id -> vocabulary id
+    DS_VOC_INV,          // decode_run: the inverse table of bpe_gpu_decode_docs_vocab
+    DS_VOC_ERR,          // bpe_gpu_map_ids: error word
     DS_COUNT
 };
 // bpe_gpu_train_split takes its eight token-sized arrays as one run of slots
