@@ -35,6 +35,10 @@ COBJ_SPECIAL := $(patsubst $(PKG)/src/%.c,$(BUILD)/%.o,$(CSRC_SPECIAL) $(CSRC_SP
 CSRC_VOCAB := $(PKG)/src/bpe_vocab.c
 CSRC_VOCAB_GPU := $(PKG)/src/bpe_vocab_gpu.c
 COBJ_VOCAB := $(patsubst $(PKG)/src/%.c,$(BUILD)/%.o,$(CSRC_VOCAB) $(CSRC_VOCAB_GPU))
+# text batches: src/bpe_texts.c is host code alone (the offsets' check and the gapped bytes; no engine call, so
+# tests/asan_texts needs no model)
+CSRC_TEXTS := $(PKG)/src/bpe_texts.c
+COBJ_TEXTS := $(patsubst $(PKG)/src/%.c,$(BUILD)/%.o,$(CSRC_TEXTS))
 HIPDEPS := $(wildcard $(PKG)/csrc/*.hip $(PKG)/csrc/*.h) $(PKG)/src/bpe_split_presets.h include/bpe_gpu.h
 
 all: $(PKG)/libbpe_amd.so tools/bpe_main oracle
@@ -48,7 +52,7 @@ $(BUILD)/engine.o: $(HIPDEPS) | $(BUILD)
 $(BUILD)/%.o: $(PKG)/src/%.c $(wildcard include/*.h $(PKG)/src/*.h $(PKG)/csrc/unicode_classes.h) | $(BUILD)
 	$(CC) $(CFLAGS) -c $< -o $@
 
-$(PKG)/libbpe_amd.so: $(BUILD)/engine.o $(COBJ) $(COBJ_GPU) $(COBJ_TS) $(COBJ_SP) $(COBJ_SPECIAL) $(COBJ_VOCAB)
+$(PKG)/libbpe_amd.so: $(BUILD)/engine.o $(COBJ) $(COBJ_GPU) $(COBJ_TS) $(COBJ_SP) $(COBJ_SPECIAL) $(COBJ_VOCAB) $(COBJ_TEXTS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -lm -ldl -lpthread
 
 tools/bpe_main: tools/bpe_main.c $(PKG)/libbpe_amd.so
@@ -142,3 +146,12 @@ tests/asan_vocab/asan_vocab: tests/asan_vocab/asan_vocab.c $(CSRC_VOCAB) $(wildc
 
 asan-vocab: tests/asan_vocab/asan_vocab
 .PHONY: asan-vocab
+
+# the text batches' host code (src/bpe_texts.c: bpe_texts_check and bpe_texts_gap) the same way, in a stand-alone
+# program that calls no engine function (tests/asan_texts/asan_texts.c); run by tests/test_asan_texts.py
+tests/asan_texts/asan_texts: tests/asan_texts/asan_texts.c $(CSRC_TEXTS) $(wildcard include/*.h)
+	$(CC) -O1 -g -std=c11 -D_GNU_SOURCE -fno-omit-frame-pointer -fsanitize=address,undefined \
+	    -fno-sanitize-recover=undefined -Iinclude -o $@ tests/asan_texts/asan_texts.c $(CSRC_TEXTS) -lm
+
+asan-texts: tests/asan_texts/asan_texts
+.PHONY: asan-texts

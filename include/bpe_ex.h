@@ -144,6 +144,22 @@ char *bpe_decode_docs_vocab(const uint32_t *ids, size_t len, const uint64_t *id_
                             const bpe_gpu_specials *specials, const bpe_gpu_vocab *vocab, int device, size_t *out_len,
                             uint64_t **byte_off);
 
+/* Text batches (bpe_gpu.h, "Text batches").  bpe_texts_check: 0 when text_off[0 .. T] are the byte offsets of T
+ * texts in n bytes: text_off[0] == 0, none below the one before it, text_off[T] == n, and n + T (a gap byte per
+ * text) at most BPE_TEXTS_MAX_POSITIONS; else BPE_GPU_EINVAL and, unless msg is NULL, a message in
+ * msg[0 .. msg_cap) that names the offending offset by its index.  No GPU. */
+#define BPE_TEXTS_MAX_POSITIONS 0xFFFFFFFEull
+int bpe_texts_check(const uint64_t *text_off, size_t T, size_t n, char *msg, size_t msg_cap);
+/* The bytes as a context keeps a text batch: out[0 .. n + T) = every text followed by one gap byte 0x00, so
+ * text k begins at text_off[k] + k and its gap is position text_off[k + 1] + k.  BPE_GPU_EINVAL for offsets
+ * bpe_texts_check refuses or out_cap < n + T.  No GPU. */
+int bpe_texts_gap(const uint8_t *bytes, size_t n, const uint64_t *text_off, size_t T, uint8_t *out, size_t out_cap);
+/* ... and the stretch [lo, hi) of them alone: out[0 .. hi - lo).  The offsets must be ones bpe_texts_check accepts
+ * (they are not checked again: bpe_gpu_load_texts calls this per chunk and thread); BPE_GPU_EINVAL for
+ * lo > hi or hi > n + T.  No GPU. */
+int bpe_texts_gap_range(const uint8_t *bytes, size_t n, const uint64_t *text_off, size_t T, size_t lo, size_t hi,
+                        uint8_t *out);
+
 /* statistics of the last compress/compress_ex/bpe_train_bytes/bpe_encode_bytes/bpe_encode_docs/bpe_encode_split(_preset) */
 int bpe_last_stats(bpe_gpu_stats *out);
 

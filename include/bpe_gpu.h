@@ -545,6 +545,60 @@ int bpe_gpu_decode_docs_vocab(bpe_gpu_ctx *ctx, const uint32_t *ids, size_t len,
                               const bpe_gpu_vocab *vocab, uint8_t *out, size_t cap, size_t *out_len,
                               uint64_t *byte_off);
 
+/* ------------------------------------------------------------------------
+ * Text batches: T texts in one context, each split and encoded on its own.  (A
+ * batch member is a text; "doc" keeps meaning a piece, as in bpe_gpu_encode_docs.)
+ *
+ * The contract.  For texts t[0 .. T) (any bytes, NUL included, length 0 allowed)
+ * the pieces of text k are those of a split of t[k] alone and its ids those of an
+ * encode of t[k] alone: no piece, special match, merge or UTF-8 sequence reaches
+ * across the break between two texts; seen from inside a text, the break before
+ * it is the start of a text and the break after it the end of one.  An empty text
+ * has no piece and no id.  The batch's pieces and ids are the texts' in order;
+ * text_off[0 .. T] counts the ids, text_off[0] == 0 and text_off[T] == their
+ * number.  Byte offsets handed out (bpe_gpu_fetch_split_offsets) count the bytes
+ * of the texts joined with nothing between them.
+ *
+ * How.  bpe_gpu_load_texts keeps the texts with one gap byte 0x00 after each
+ * (n + T resident bytes, built on the host by bpe_ex.h bpe_texts_gap) and the
+ * offsets on the device.  Every split of such a context (bpe_gpu_split,
+ * _split_preset, _split_special) treats gap k, at resident position
+ * text_off[k + 1] + k, as it treats a special's match: a covered byte that ends
+ * the segment before it and begins one after it.  The offsets alone say where a
+ * gap is; a NUL inside a text is an ordinary byte, and since no special holds a
+ * NUL none matches across a gap.  In the match list a break carries the reserved
+ * index 255 (BPE_GPU_TEXT_BREAK): a split of a text batch therefore takes at most
+ * 255 specials, and 256 are refused with BPE_GPU_EINVAL by that name.
+ * bpe_gpu_encode_split removes every id of a break piece, writes text_off where
+ * they vanished and drops the break pieces from the id offsets;
+ * bpe_gpu_fetch_split_offsets, _fetch_doc_offsets, _fetch_special_pieces and
+ * _split_special_info report the pieces without the breaks.  bpe_gpu_map_ids
+ * works as ever: no id of a break is left.
+ *
+ * Lifetime.  The breaks belong to the bytes: bpe_gpu_load, _load_fd, _synth and
+ * _trim end the text batch.  While it stands, bpe_gpu_encode, bpe_gpu_train,
+ * _train_ex, bpe_gpu_encode_docs and bpe_gpu_train_split return BPE_GPU_ESTATE
+ * (they would read the gap bytes as text; training on text batches is not
+ * offered).  A context loaded any other way launches what it always launched.
+ * ---------------------------------------------------------------------- */
+#define BPE_GPU_TEXT_BREAK 255
+/* Load T texts: text k is bytes[text_off[k] .. text_off[k + 1]).  BPE_GPU_EINVAL, with the offending index in
+   the message, for offsets bpe_texts_check (bpe_ex.h) refuses: the first not 0, one below the one before it,
+   the last not n, or n + T above 2^32 - 2. */
+int bpe_gpu_load_texts(bpe_gpu_ctx *ctx, const uint8_t *bytes, size_t n, const uint64_t *text_off, size_t T);
+/* text_off of the last bpe_gpu_encode_split over a text batch; out may be NULL, *count = T + 1.
+   BPE_GPU_ESTATE without a text batch or before its encode. */
+int bpe_gpu_fetch_text_offsets(bpe_gpu_ctx *ctx, uint64_t *out, size_t cap, size_t *count);
+/* The resident ids (mapped or not) as rows: out[T][row_len] uint32 and lens[T] uint32 (k_pack_rows).
+   lens[k] = min(ids of text k, row_len); a longer text keeps its first row_len ids (side 0) or its last
+   (side 1); pad_id, any uint32, fills the row behind the ids.  out_is_device != 0: out and lens are device
+   pointers on the context's device (a tensor's data pointer), written on the context's stream, which is
+   synchronised before the call returns; else host memory, filled through a device buffer.  lens may be NULL.
+   BPE_GPU_EINVAL for row_len == 0, another side or a device pointer that is none of this device;
+   BPE_GPU_ERANGE for row_len above 2^24; BPE_GPU_ESTATE without a text batch or without its ids. */
+int bpe_gpu_pack_texts(bpe_gpu_ctx *ctx, uint32_t row_len, uint32_t pad_id, int side, uint32_t *out,
+                       int out_is_device, uint32_t *lens);
+
 int bpe_gpu_get_stats(bpe_gpu_ctx *ctx, bpe_gpu_stats *st);
 
 /* Position-keyed checksum of the ids of the last train / encode, computed in

@@ -53,6 +53,9 @@ EXPORTS = [
     # bpe_gpu.h / bpe_ex.h: vocabularies
     "bpe_gpu_map_ids", "bpe_gpu_map_info", "bpe_gpu_decode_docs_vocab", "bpe_vocab_check", "bpe_vocab_tables",
     "bpe_encode_split_vocab", "bpe_decode_docs_vocab",
+    # bpe_gpu.h / bpe_ex.h: text batches
+    "bpe_gpu_load_texts", "bpe_gpu_fetch_text_offsets", "bpe_gpu_pack_texts", "bpe_texts_check", "bpe_texts_gap",
+    "bpe_texts_gap_range",
 ]
 
 
@@ -264,6 +267,12 @@ def load():
     L.bpe_decode_docs_vocab.argtypes = [vp, sz, vp, sz, ctypes.POINTER(DynArr), spp, vop, ctypes.c_int,
                                         ctypes.POINTER(sz), ctypes.POINTER(u64p)]
     L.bpe_decode_docs_vocab.restype = ctypes.c_void_p
+    L.bpe_gpu_load_texts.argtypes = [vp, vp, sz, vp, sz]
+    L.bpe_gpu_fetch_text_offsets.argtypes = [vp, vp, sz, ctypes.POINTER(sz)]
+    L.bpe_gpu_pack_texts.argtypes = [vp, ctypes.c_uint32, ctypes.c_uint32, ctypes.c_int, vp, ctypes.c_int, vp]
+    L.bpe_texts_check.argtypes = [vp, sz, sz, ctypes.c_char_p, sz]
+    L.bpe_texts_gap.argtypes = [vp, sz, vp, sz, vp, sz]
+    L.bpe_texts_gap_range.argtypes = [vp, sz, vp, sz, sz, sz, vp]
     L.bpe_release_engines.argtypes = []
     L.bpe_release_engines.restype = None
     _LIB = L

@@ -464,6 +464,50 @@ def read_pairs(path):
         L.dyn_arr_free(arr)
 
 
+def _join_texts(texts):
+    """(the texts joined as uint8, their byte offsets uint64[T + 1]); a str is encoded as UTF-8"""
+    items = [t.encode("utf-8") if isinstance(t, str) else bytes(t) for t in texts]
+    off = np.zeros(len(items) + 1, dtype=np.uint64)
+    if items:
+        off[1:] = np.cumsum(np.fromiter((len(t) for t in items), dtype=np.uint64, count=len(items)))
+    return np.frombuffer(b"".join(items), dtype=np.uint8), off
+
+
+def check_texts(text_off, n):
+    """Raise BpeError unless text_off are the byte offsets of len(text_off) - 1 texts in n bytes: the first 0, rising,
+    the last n, n plus a gap byte per text within the 2^32 - 2 positions of a context (bpe_ex.h bpe_texts_check).
+    The message names the offending index.  No GPU."""
+    off = np.ascontiguousarray(text_off, dtype=np.uint64).reshape(-1)
+    if off.size < 1:
+        raise BpeError("texts: offsets must hold len(texts) + 1 entries")
+    msg = ctypes.create_string_buffer(400)
+    if _lib.load().bpe_texts_check(off.ctypes.data_as(ctypes.c_void_p), off.size - 1, int(n), msg, len(msg)):
+        raise BpeError(msg.value.decode(errors="replace"))
+    return off
+
+
+def texts_gap(data, text_off, lo=None, hi=None):
+    """The bytes a context keeps of a text batch: every text followed by one gap byte 0x00 (bpe_ex.h bpe_texts_gap);
+    with lo / hi the stretch [lo, hi) of them alone (bpe_texts_gap_range).  No GPU."""
+    buf = np.frombuffer(bytes(data), dtype=np.uint8)
+    off = check_texts(text_off, buf.size)
+    total = buf.size + off.size - 1
+    vp = ctypes.c_void_p
+    if lo is None and hi is None:
+        out = np.full(total, 0xAA, dtype=np.uint8)
+        _lib.check(_lib.load().bpe_texts_gap(buf.ctypes.data_as(vp), buf.size, off.ctypes.data_as(vp), off.size - 1,
+                                             out.ctypes.data_as(vp), out.size), "texts_gap")
+        return out.tobytes()
+    lo, hi = int(lo or 0), total if hi is None else int(hi)
+    out = np.full(max(hi - lo, 0), 0xAA, dtype=np.uint8)
+    _lib.check(_lib.load().bpe_texts_gap_range(buf.ctypes.data_as(vp), buf.size, off.ctypes.data_as(vp), off.size - 1,
+                                               lo, hi, out.ctypes.data_as(vp)), "texts_gap")
+    return out.tobytes()
+
+
+PACK_SIDES = {"right": 0, "left": 1}  # the side a longer text is cut at: "right" keeps its first ids, "left" its last
+
+
 class Engine:
     """Direct handle on one GPU context (bpe_gpu.h) -- used by bench.py to keep
     the corpus resident in HBM and time the training loop alone."""
@@ -487,6 +531,65 @@ class Engine:
     def load(self, data: bytes):
         buf = np.frombuffer(data, dtype=np.uint8)
         _lib.check(self.L.bpe_gpu_load(self.ctx, buf.ctypes.data_as(ctypes.c_void_p), buf.size), "load")
+
+    def load_texts(self, texts, offsets=None):
+        """load a batch of texts (bytes-like objects; a str is encoded as UTF-8), each to be split and encoded on
+        its own (bpe_gpu_load_texts): split() and encode_split() then honour the breaks between them, ids(),
+        doc_offsets() and split_offsets() describe the texts joined with nothing between them, and
+        text_offsets() / pack_texts() give the ids per text.  Any other load ends the batch.  With offsets
+        (uint64, texts + 1 entries) `texts` is the texts' bytes already joined.  Returns the number of texts."""
+        if offsets is None:
+            buf, off = _join_texts(texts)
+        else:
+            buf, off = np.frombuffer(texts, dtype=np.uint8), _doc_offsets(offsets)
+            if off.size < 1:
+                raise BpeError("load_texts: offsets must hold len(texts) + 1 entries")
+        vp = ctypes.c_void_p
+        _lib.check(self.L.bpe_gpu_load_texts(self.ctx, buf.ctypes.data_as(vp), buf.size, off.ctypes.data_as(vp),
+                                             off.size - 1), "load_texts")
+        return off.size - 1
+
+    def text_offsets(self):
+        """id offsets of the texts after encode_split() over a text batch (uint64, texts + 1 entries:
+        text k's ids are ids()[text_offsets()[k]:text_offsets()[k + 1]]; bpe_gpu_fetch_text_offsets)"""
+        n = ctypes.c_size_t(0)
+        _lib.check(self.L.bpe_gpu_fetch_text_offsets(self.ctx, None, 0, ctypes.byref(n)), "fetch_text_offsets")
+        out = np.zeros(n.value, dtype=np.uint64)
+        _lib.check(self.L.bpe_gpu_fetch_text_offsets(self.ctx, out.ctypes.data_as(ctypes.c_void_p), n.value,
+                                                     ctypes.byref(n)), "fetch_text_offsets")
+        return out
+
+    def pack_texts(self, row_len, pad_id, side="right", out=None):
+        """the resident ids of a text batch (mapped or not) as rows (bpe_gpu_pack_texts): (rows uint32[texts, row_len],
+        lens uint32[texts]) with lens[k] = min(ids of text k, row_len); a longer text is cut at `side` ("right": its
+        first row_len ids stay, "left": its last), pad_id (any uint32) fills the row behind the ids.  Returns numpy
+        arrays.  out: a contiguous torch tensor of 32-bit integers, [texts, row_len], on this engine's device: the
+        rows are written into it on the device, no id passes through the host, and (out, lens), lens a torch int32
+        tensor beside it, is returned."""
+        if side not in PACK_SIDES:
+            raise BpeError(f"pack_texts: side {side!r} (have {sorted(PACK_SIDES)})")
+        row_len, pad_id = int(row_len), int(pad_id)
+        if not 0 <= pad_id <= 0xFFFFFFFF or not 0 <= row_len <= 0xFFFFFFFF:
+            raise BpeError("pack_texts: row_len and pad_id are uint32")
+        T = self.text_offsets().size - 1
+        vp = ctypes.c_void_p
+        if out is None:
+            rows = np.zeros((T, row_len), dtype=np.uint32)
+            lens = np.zeros(T, dtype=np.uint32)
+            _lib.check(self.L.bpe_gpu_pack_texts(self.ctx, row_len, pad_id, PACK_SIDES[side],
+                                                 rows.ctypes.data_as(vp) if rows.size else None, 0,
+                                                 lens.ctypes.data_as(vp) if T else None), "pack_texts")
+            return rows, lens
+        import torch
+        if (not isinstance(out, torch.Tensor) or not out.is_cuda or out.element_size() != 4 or out.is_floating_point()
+                or tuple(out.shape) != (T, row_len) or not out.is_contiguous()):
+            raise BpeError(f"pack_texts: out must be a contiguous 32-bit integer tensor of shape ({T}, {row_len}) on the GPU")
+        lens = torch.empty(T, dtype=torch.int32, device=out.device)
+        torch.cuda.current_stream(out.device).synchronize()  # (the call writes on the context's stream)
+        _lib.check(self.L.bpe_gpu_pack_texts(self.ctx, row_len, pad_id, PACK_SIDES[side],
+                                             vp(out.data_ptr()) if out.numel() else None, 1,
+                                             vp(lens.data_ptr()) if T else None), "pack_texts")
+        return out, lens
 
     def load_file(self, path):
         """stream a file into HBM (bpe_gpu_load_fd: pinned double-buffered

@@ -13,6 +13,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <thread>
 #include <vector>
@@ -30,7 +31,12 @@
 #include "train_split.hip"
 #include "special.hip"
 #include "vocab.hip"
+#include "texts.hip"
 
+// (bpe_ex.h, src/bpe_texts.c: the host definition of a text batch's offsets and its resident bytes)
+extern "C" int bpe_texts_check(const uint64_t *text_off, size_t T, size_t n, char *msg, size_t msg_cap);
+extern "C" int bpe_texts_gap_range(const uint8_t *bytes, size_t n, const uint64_t *text_off, size_t T, size_t lo, size_t hi,
+                                   uint8_t *out);
 // (bpe_ex.h, src/bpe_special.c: the host definition of a valid set)
 extern "C" int bpe_specials_check(const bpe_gpu_specials *specials, char *msg, size_t msg_cap);
 // (bpe_ex.h, src/bpe_vocab.c: the host definition of a valid vocabulary and its two tables)
@@ -321,6 +327,11 @@ struct bpe_gpu_ctx {
     unsigned long long *d_sp_pieces = nullptr;
     size_t sp_cap = 0;  // entries d_sp_pieces holds
     uint64_t sp_info[4] = {};
+    // a text batch (bpe_gpu_load_texts): h.bytes holds every text followed by a gap byte, n0 counts them, and
+    // scratch slot DS_TX_BOFF the texts' offsets.  It goes with the bytes (alloc_bytes, bpe_gpu_trim).  While
+    // split_ready, split_n counts the break pieces too and DS_TX_PIECE / DS_TX_SPLIT hold what split_run left.
+    bool tx_on = false;
+    uint64_t tx_T = 0;
     // the last bpe_gpu_train_split over those offsets: its merges (host), bpe_gpu_train_split_info's fields and
     // the piece table (scratch slots DS_TS_ESTART, DS_TS_ELEN, DS_TS_ECNT).  Valid while split_ready: whatever drops
     // the offsets drops these.
@@ -2596,6 +2607,8 @@ static int alloc_bytes(bpe_gpu_ctx *c, size_t n) {
     free_train(c, !same);
     c->pres_valid = false;
     c->split_ready = false;  // the split's offsets describe the bytes replaced here
+    c->tx_on = false;        // ... and so do a text batch's breaks
+    c->tx_T = 0;
     if (!c->h.bytes || c->bytes_cap < n + 64) {  // (a buffer at least this large is kept)
         if (c->h.bytes) { (void)hipFree(c->h.bytes); c->h.bytes = nullptr; }
         HIPCHK(hipMalloc(&c->h.bytes, n + 64));
@@ -2630,6 +2643,57 @@ int bpe_gpu_load(bpe_gpu_ctx *c, const uint8_t *bytes, size_t n) {
     return 0;
 }
 
+int bpe_gpu_load_texts(bpe_gpu_ctx *c, const uint8_t *bytes, size_t n, const uint64_t *text_off, size_t T) {
+    if (!c || (!bytes && n) || !text_off) return BPE_GPU_EINVAL;
+    char msg[400];
+    if (bpe_texts_check(text_off, T, n, msg, sizeof msg)) return fail(BPE_GPU_EINVAL, msg);
+    HIPCHK(hipSetDevice(c->dev));
+    // The resident bytes are built on the host (src/bpe_texts.c: a memcpy per text), 64 MiB at a time in the two
+    // pinned staging buffers, by several threads each (one is bound by its memcpy), a chunk's upload under the
+    // next chunk's building, as bpe_gpu_load_fd stages a file.
+    const size_t nres = n + T;
+    int r;
+    uint64_t *boff;
+    if ((r = alloc_bytes(c, nres)) || (r = dscratch(c, DS_TX_BOFF, (T + 1) * 8, &boff))) return r;
+    HIPCHK(hipMemcpyAsync(boff, text_off, (T + 1) * 8, hipMemcpyHostToDevice, c->st));
+    constexpr size_t CH = 64u << 20;
+    const bool small = nres < (8u << 20);  // (as d2h_staged: not worth the pinned buffers)
+    if (small && nres) {
+        std::vector<uint8_t> whole(nres);
+        (void)bpe_texts_gap_range(bytes, n, text_off, T, 0, nres, whole.data());
+        const hipError_t e = hipMemcpyAsync(c->h.bytes, whole.data(), nres, hipMemcpyHostToDevice, c->st);
+        const hipError_t e2 = hipStreamSynchronize(c->st);  // (whichever way this ends, the copy is over before `whole` goes)
+        HIPCHK(e);
+        HIPCHK(e2);
+    }
+    for (int k = 0; k < 2 && !small; k++) {
+        if (!c->stage[k]) HIPCHK(hipHostMalloc((void **)&c->stage[k], CH, hipHostMallocDefault));
+        if (!c->stage_ev[k]) HIPCHK(hipEventCreateWithFlags(&c->stage_ev[k], hipEventDisableTiming));
+    }
+    const int nthr = std::max(1, std::min(32, getenv_int("BPE_LOAD_THREADS", 16)));
+    std::vector<std::thread> pool;
+    for (size_t k = 0, lo = 0; lo < nres && !small; k++, lo += CH) {
+        uint8_t *buf = c->stage[k & 1];
+        if (k >= 2) HIPCHK(hipEventSynchronize(c->stage_ev[k & 1]));  // its previous copy is done
+        const size_t len = std::min(CH, nres - lo);
+        const size_t step = ((len + nthr - 1) / nthr + 4095) & ~(size_t)4095;
+        pool.clear();
+        for (int t = 1; t < nthr; t++) {
+            const size_t a = std::min(len, (size_t)t * step), b = std::min(len, a + step);
+            if (b > a) pool.emplace_back([=] { (void)bpe_texts_gap_range(bytes, n, text_off, T, lo + a, lo + b, buf + a); });
+        }
+        (void)bpe_texts_gap_range(bytes, n, text_off, T, lo, lo + std::min(len, step), buf);
+        for (auto &th : pool) th.join();
+        HIPCHK(hipMemcpyAsync(c->h.bytes + lo, buf, len, hipMemcpyHostToDevice, c->st));
+        HIPCHK(hipEventRecord(c->stage_ev[k & 1], c->st));
+    }
+    if ((r = ingest_presence(c, nres))) return r;
+    HIPCHK(hipStreamSynchronize(c->st));
+    c->tx_on = true;
+    c->tx_T = T;
+    return 0;
+}
+
 int bpe_gpu_synth(bpe_gpu_ctx *c, uint64_t seed, size_t n, uint64_t offset) {
     if (!c) return BPE_GPU_EINVAL;
     HIPCHK(hipSetDevice(c->dev));
@@ -2649,6 +2713,7 @@ int bpe_gpu_train(bpe_gpu_ctx *c, long max_merges, size_t *n_merges) {
 int bpe_gpu_train_ex(bpe_gpu_ctx *c, long max_merges, unsigned flags, size_t *n_merges) {
     if (!c || !n_merges) return BPE_GPU_EINVAL;
     if (!c->loaded) return fail(BPE_GPU_ESTATE, "train before load");
+    if (c->tx_on) return fail(BPE_GPU_ESTATE, "train: the context holds a text batch (bpe_gpu_load_texts): its gap bytes are no text, and training on text batches is not offered");
     if (flags & ~(unsigned)BPE_GPU_FAST) return fail(BPE_GPU_EINVAL, "unknown train flag");
     HIPCHK(hipSetDevice(c->dev));
     c->fast = (flags & BPE_GPU_FAST) ? 1 : 0;
@@ -2832,6 +2897,7 @@ int bpe_gpu_fetch_ids_range(bpe_gpu_ctx *c, size_t first, uint32_t *ids, size_t 
 int bpe_gpu_encode(bpe_gpu_ctx *c, const uint32_t *pairs, size_t n_merges) {
     if (!c || (!pairs && n_merges)) return BPE_GPU_EINVAL;
     if (!c->loaded) return fail(BPE_GPU_ESTATE, "encode before load");
+    if (c->tx_on) return fail(BPE_GPU_ESTATE, "encode: the context holds a text batch (bpe_gpu_load_texts): its gap bytes are no text; split it and use bpe_gpu_encode_split");
     if (n_merges > 0xFFFFFEFFull) return fail(BPE_GPU_ERANGE, "merge list too long");
     HIPCHK(hipSetDevice(c->dev));
     c->stats = bpe_gpu_stats{};
@@ -3286,6 +3352,8 @@ int bpe_gpu_trim(bpe_gpu_ctx *c) {
     c->sp_cap = 0;
     c->sp_S = 0;
     c->sp_M = 0;
+    c->tx_on = false;
+    c->tx_T = 0;
     for (int k = 0; k < DS_COUNT; k++) {
         if (c->dscr[k]) (void)hipFree(c->dscr[k]);
         c->dscr[k] = nullptr;
@@ -3481,6 +3549,7 @@ extern "C" {
 int bpe_gpu_encode_docs(bpe_gpu_ctx *c, const uint64_t *doc_off, size_t ndocs, const uint32_t *pairs, size_t n_merges) {
     if (!c || !doc_off || (!pairs && n_merges)) return BPE_GPU_EINVAL;
     if (!c->loaded) return fail(BPE_GPU_ESTATE, "encode before load");
+    if (c->tx_on) return fail(BPE_GPU_ESTATE, "encode_docs: the context holds a text batch (bpe_gpu_load_texts): its gap bytes are no text; split it and use bpe_gpu_encode_split");
     if (n_merges > 0xFFFFFEFFull) return fail(BPE_GPU_ERANGE, "merge list too long");
     const uint64_t n = c->n0;
     const double t_chk = now_ms();
@@ -3612,6 +3681,69 @@ int bpe_gpu_decode_docs_vocab(bpe_gpu_ctx *c, const uint32_t *ids, size_t len, c
         return decode_run(c, ids, len, pairs, n_merges, specials, out, cap, out_len, vocab);
     }
     return decode_docs_run(c, ids, len, id_off, ndocs, pairs, n_merges, specials, out, cap, out_len, byte_off, vocab);
+}
+
+// ------------------------------------------------ text batches (texts.hip; the split and the encode: pieces.hip)
+
+int bpe_gpu_fetch_text_offsets(bpe_gpu_ctx *c, uint64_t *out, size_t cap, size_t *count) {
+    if (!c || !count) return BPE_GPU_EINVAL;
+    if (!c->tx_on) return fail(BPE_GPU_ESTATE, "no text offsets: the context holds no text batch (bpe_gpu_load_texts)");
+    if (!c->ids_ready || !c->docs_ready) return fail(BPE_GPU_ESTATE, "no text offsets: encode_split first");
+    HIPCHK(hipSetDevice(c->dev));
+    *count = c->tx_T + 1;
+    const size_t k = out ? std::min<size_t>(cap, c->tx_T + 1) : 0;
+    if (k) return d2h_staged(c, out, c->dscr[DS_TX_IDOFF], k * 8);
+    return 0;
+}
+
+int bpe_gpu_pack_texts(bpe_gpu_ctx *c, uint32_t row_len, uint32_t pad_id, int side, uint32_t *out, int out_is_device,
+                       uint32_t *lens) {
+    if (!c) return BPE_GPU_EINVAL;
+    if (row_len == 0) return fail(BPE_GPU_EINVAL, "pack_texts: row_len is 0");
+    if (side != 0 && side != 1) return fail(BPE_GPU_EINVAL, "pack_texts: side is neither 0 (keep the first ids) nor 1 (the last)");
+    if (row_len > PK_ROW_MAX) return fail(BPE_GPU_ERANGE, "pack_texts: row_len above 2^24");
+    if (!c->tx_on) return fail(BPE_GPU_ESTATE, "pack_texts: the context holds no text batch (bpe_gpu_load_texts)");
+    if (!c->ids_ready || !c->docs_ready) return fail(BPE_GPU_ESTATE, "pack_texts: no ids: encode_split first");
+    const uint64_t T = c->tx_T;
+    if (!T) return 0;
+    if (!out) return fail(BPE_GPU_EINVAL, "pack_texts: no output");
+    HIPCHK(hipSetDevice(c->dev));
+    const size_t cells = (size_t)T * row_len;
+    uint32_t *d_out = out, *d_lens = lens;
+    if (out_is_device) {
+        for (const void *p : {(const void *)out, (const void *)lens}) {
+            if (!p) continue;
+            hipPointerAttribute_t at;
+            if (hipPointerGetAttributes(&at, p) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != c->dev) {
+                (void)hipGetLastError();
+                return fail(BPE_GPU_EINVAL, "pack_texts: out / lens is no device pointer of the context's device");
+            }
+        }
+        if (((uintptr_t)out & 3u) || ((uintptr_t)lens & 3u)) return fail(BPE_GPU_EINVAL, "pack_texts: a pointer that is not 4-byte aligned");
+    } else {
+        int r;
+        if ((r = dscratch(c, DS_TX_PACK, (cells + T) * 4, &d_out))) return r;
+        d_lens = d_out + cells;
+    }
+    // the workgroup's shape: bx lanes along a row (a power of two, one or four columns each), by rows
+    const bool vec = row_len % 4 == 0 && ((uintptr_t)d_out & 15u) == 0;
+    const uint32_t units = vec ? row_len / 4 : row_len;
+    uint32_t bx = 1;
+    while (bx < units && bx < PK_T) bx *= 2;
+    const uint32_t by = PK_T / bx, gx = (units + bx - 1) / bx;
+    const uint32_t gy = (uint32_t)std::min<uint64_t>({(T + by - 1) / by, (uint64_t)65535, (uint64_t)std::max<uint32_t>(PK_BLOCKS / gx, 1)});
+    const uint32_t *ids = c->h.ids_out;
+    const uint64_t *toff = (const uint64_t *)c->dscr[DS_TX_IDOFF];
+    if (vec) k_pack_rows<true><<<dim3(gx, gy), dim3(bx, by), 0, c->st>>>(ids, toff, T, row_len, pad_id, (uint32_t)side, d_out, d_lens);
+    else k_pack_rows<false><<<dim3(gx, gy), dim3(bx, by), 0, c->st>>>(ids, toff, T, row_len, pad_id, (uint32_t)side, d_out, d_lens);
+    HIPCHK(hipGetLastError());
+    if (!out_is_device) {
+        int r;
+        if ((r = d2h_staged(c, out, d_out, cells * 4))) return r;
+        if (lens && (r = d2h_staged(c, lens, d_lens, T * 4))) return r;
+    }
+    HIPCHK(hipStreamSynchronize(c->st));
+    return 0;
 }
 
 }  // extern "C"

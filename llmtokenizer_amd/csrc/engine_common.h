@@ -667,6 +667,11 @@ enum DScr {
     DS_VOC_FWD,          // bpe_gpu_map_ids: the forward table, internal id -> vocabulary id
     DS_VOC_INV,          // decode_run: the inverse table of bpe_gpu_decode_docs_vocab
     DS_VOC_ERR,          // bpe_gpu_map_ids: error word
+    DS_TX_BOFF,          // bpe_gpu_load_texts: the texts' byte offsets in the plain join [T + 1]; stays with the bytes
+    DS_TX_PIECE,         // split_run: the piece index of every gap [T]; stays with the split's offsets
+    DS_TX_SPLIT,         // split_run: the split's offsets without the break pieces, in the plain join's coordinates
+    DS_TX_IDOFF,         // bpe_gpu_encode_split: text_off, the texts' id offsets [T + 1]; stays with the ids
+    DS_TX_PACK,          // bpe_gpu_pack_texts: the rows and lens of a call with host pointers
     DS_COUNT
 };
 // bpe_gpu_train_split takes its eight token-sized arrays as one run of slots

@@ -70,7 +70,9 @@ struct SpFound {
 // The special passes of a split (special.hip).  sp_find: the matches; it runs after the marking kernel, or before
 // it for a marker whose kernel reads the cover bitmap (Marker::specials_first).  sp_patch, between the marking
 // kernel and the count scan when there are matches: patch, recount and sort.
-static int sp_find(bpe_gpu_ctx *c, const SpSet *sp, uint64_t n, uint64_t ntiles, uint32_t grid, SpFound *F, uint64_t *info) {
+// T, boff: the gaps of a text batch (texts.hip), which join the list behind the matches as breaks; T == 0: none
+static int sp_find(bpe_gpu_ctx *c, const SpSet *sp, uint64_t n, uint64_t ntiles, uint32_t grid, SpFound *F, uint64_t *info,
+                   uint64_t T = 0, const uint64_t *boff = nullptr) {
     int r;
     const size_t cov_bytes = ntiles * SP_T * 2;  // a bit per byte of the whole tiles
     if ((r = dscratch(c, DS_SP_SET, sizeof(SpSet), &F->set)) || (r = dscratch(c, DS_SP_COVER, cov_bytes, &F->cover)) ||
@@ -81,8 +83,9 @@ static int sp_find(bpe_gpu_ctx *c, const SpSet *sp, uint64_t n, uint64_t ntiles,
     // room for a match every 256 bytes; a text with more runs the pass again with the room it counted
     uint64_t cap = n / 256 + 1024;
     for (int pass = 1;; pass++) {
-        if ((r = dscratch(c, DS_SP_LIST, cap * 8, &F->list))) return r;
+        if ((r = dscratch(c, DS_SP_LIST, (cap + T) * 8, &F->list))) return r;
         HIPCHK(hipMemsetAsync(F->ctl, 0, 64, c->st));
+        if (!sp->S) break;  // (a text batch without specials: the list holds its breaks alone)
         k_sp_find<<<grid, SP_T, 0, c->st>>>(c->h.bytes, n, ntiles, F->set, F->cover, F->list,
                                             (uint32_t)std::min<uint64_t>(cap, 0xFFFFFFFFull), F->ctl);
         HIPCHK(hipGetLastError());
@@ -95,6 +98,11 @@ static int sp_find(bpe_gpu_ctx *c, const SpSet *sp, uint64_t n, uint64_t ntiles,
     }
     info[1] = F->M;
     info[3] = cap;
+    if (T) {
+        k_text_breaks<<<sx_grid(T), SX_T, 0, c->st>>>(boff, T, F->cover, F->list + F->M);
+        HIPCHK(hipGetLastError());
+        F->M += (uint32_t)T;  // (matches and gaps are distinct bytes: M + T <= n)
+    }
     return 0;
 }
 
@@ -138,6 +146,17 @@ static int split_run(bpe_gpu_ctx *c, int preset, const uint8_t *cls, const uint1
     c->ts_ready = false;  // bpe_gpu_train_split's results describe the offsets replaced here
     c->sp_S = 0;          // ... and so do the specials and their pieces
     c->sp_M = 0;
+    // a text batch: its gaps are breaks, found like matches whether or not there are specials
+    const uint64_t T = c->tx_on ? c->tx_T : 0;
+    const uint64_t *boff = (const uint64_t *)c->dscr[DS_TX_BOFF];
+    std::vector<SpSet> none;
+    if (T && !sp) {
+        none.resize(1);
+        memset(&none[0], 0, sizeof(SpSet));
+        sp = &none[0];
+    }
+    if (T && sp->S > SX_BREAK)
+        return fail(BPE_GPU_EINVAL, "split: a text batch takes at most 255 specials (index 255 is BPE_GPU_TEXT_BREAK)");
     uint64_t sp_info[4] = {sp ? sp->S : 0u, 0, 0, 0};
     SpFound F;
     const uint64_t n = c->n0, ntiles = (n + SP_TILE - 1) / SP_TILE, nwt = ntiles * (SP_T / 64);
@@ -153,7 +172,7 @@ static int split_run(bpe_gpu_ctx *c, int preset, const uint8_t *cls, const uint1
             return r;
         uint32_t *wcnt = (uint32_t *)(woff + nwt + 1);
         HIPCHK(hipMemsetAsync(wcnt + nwt, 0, 4, c->st));
-        if (sp && m.specials_first() && (r = sp_find(c, sp, n, ntiles, grid, &F, sp_info))) return r;
+        if (sp && m.specials_first() && (r = sp_find(c, sp, n, ntiles, grid, &F, sp_info, T, boff))) return r;
         switch (m.kind) {
         case MARK_TABLE:
             k_split_table<<<SP_TBL / SP_T, SP_T, 0, c->st>>>(m.tables, tbl);
@@ -171,7 +190,7 @@ static int split_run(bpe_gpu_ctx *c, int preset, const uint8_t *cls, const uint1
             break;
         }
         HIPCHK(hipGetLastError());
-        if (sp && !m.specials_first() && (r = sp_find(c, sp, n, ntiles, grid, &F, sp_info))) return r;
+        if (sp && !m.specials_first() && (r = sp_find(c, sp, n, ntiles, grid, &F, sp_info, T, boff))) return r;
         if (sp && (r = sp_patch(c, &F, m.patch_mode(), n, ntiles, grid, mask, wcnt))) return r;
         r = ROCPRIM_RUN(c, DS_SPLIT_TMP, rocprim::exclusive_scan(tmp, tb, wcnt, woff, 0ull, nwt + 1, rocprim::plus<unsigned long long>(), c->st));
         if (r) return r;
@@ -195,13 +214,29 @@ static int split_run(bpe_gpu_ctx *c, int preset, const uint8_t *cls, const uint1
         HIPCHK(hipStreamSynchronize(c->st));
         if (bad) return fail(BPE_GPU_EINTERNAL, "split_special: a match does not start a piece");
     }
+    if (c->tx_on) {  // every gap's piece, and the offsets as the caller sees them: no break piece, the plain join's bytes
+        if (total < T) return fail(BPE_GPU_EINTERNAL, "split: fewer pieces than text breaks");
+        uint64_t *bpiece, *plain;
+        uint32_t *bad, hbad = 0;
+        if ((r = dscratch(c, DS_TX_PIECE, T * 8, &bpiece)) || (r = dscratch(c, DS_TX_SPLIT, (total - T + 1) * 8, &plain)) ||
+            (r = dscratch(c, DS_SP_CTL, 64, &bad)))
+            return r;
+        HIPCHK(hipMemsetAsync(bad + 2, 0, 4, c->st));
+        if (T) k_text_pieces<<<sx_grid(T), SX_T, 0, c->st>>>(boff, T, c->d_split, total, bpiece, bad + 2);
+        HIPCHK(hipGetLastError());
+        k_text_compact<<<sx_grid(total + 1), SX_T, 0, c->st>>>(c->d_split, total, bpiece, T, 1, plain);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(&hbad, bad + 2, 4, hipMemcpyDeviceToHost, c->st));
+        HIPCHK(hipStreamSynchronize(c->st));
+        if (hbad) return fail(BPE_GPU_EINTERNAL, "split: a text break is no piece of its own");
+    }
     HIPCHK(hipStreamSynchronize(c->st));
     c->sp_S = sp ? sp->S : 0u;
     c->sp_M = F.M;
     memcpy(c->sp_info, sp_info, sizeof sp_info);
     c->split_n = total;
     c->split_ready = true;
-    *ndocs = (size_t)total;
+    *ndocs = (size_t)(total - T);
     return 0;
 }
 
@@ -293,7 +328,7 @@ int bpe_gpu_split_special_info(bpe_gpu_ctx *c, uint64_t *out4) {
     if (!c || !out4) return BPE_GPU_EINVAL;
     if (!c->loaded || !c->split_ready) return fail(BPE_GPU_ESTATE, "no split: split first");
     memset(out4, 0, 4 * sizeof(uint64_t));
-    if (c->sp_S) memcpy(out4, c->sp_info, sizeof c->sp_info);
+    if (c->sp_S) memcpy(out4, c->sp_info, sizeof c->sp_info);  // (a text batch's breaks are not counted: sp_find)
     return 0;
 }
 
@@ -301,16 +336,24 @@ int bpe_gpu_fetch_special_pieces(bpe_gpu_ctx *c, uint64_t *piece, uint32_t *inde
     if (!c || !count) return BPE_GPU_EINVAL;
     if (!c->loaded || !c->split_ready) return fail(BPE_GPU_ESTATE, "no special pieces: split first");
     HIPCHK(hipSetDevice(c->dev));
-    const uint64_t M = c->sp_S ? c->sp_M : 0;
-    *count = (size_t)M;
-    const size_t k = std::min<size_t>(cap, (size_t)M);
+    const uint64_t T = c->tx_on ? c->tx_T : 0;
+    const uint64_t M = c->sp_S ? c->sp_M : 0;  // (of a text batch: the breaks among them)
+    *count = (size_t)(M ? M - T : 0);
+    const size_t k = std::min<size_t>(cap, *count);
     if (!k || (!piece && !index)) return 0;
-    std::vector<unsigned long long> h(k);
-    const int r = d2h_staged(c, h.data(), c->d_sp_pieces, k * 8);
+    // a text batch: the list holds the break pieces too, which are skipped, and the pieces are numbered without them
+    std::vector<unsigned long long> h(T ? (size_t)M : k);
+    const int r = d2h_staged(c, h.data(), c->d_sp_pieces, h.size() * 8);
     if (r) return r;
-    for (size_t m = 0; m < k; m++) {
-        if (piece) piece[m] = h[m] >> 8;
-        if (index) index[m] = (uint32_t)(h[m] & 0xFFull);
+    size_t breaks = 0, at = 0;
+    for (size_t m = 0; m < h.size() && at < k; m++) {
+        if (T && (h[m] & 0xFFull) == SX_BREAK) {
+            breaks++;
+            continue;
+        }
+        if (piece) piece[at] = (h[m] >> 8) - breaks;
+        if (index) index[at] = (uint32_t)(h[m] & 0xFFull);
+        at++;
     }
     return 0;
 }
@@ -319,42 +362,55 @@ int bpe_gpu_fetch_split_offsets(bpe_gpu_ctx *c, uint64_t *out, size_t cap, size_
     if (!c || !count) return BPE_GPU_EINVAL;
     if (!c->loaded || !c->split_ready) return fail(BPE_GPU_ESTATE, "no split offsets: split first");
     HIPCHK(hipSetDevice(c->dev));
-    *count = c->split_n + 1;
-    const size_t k = out ? std::min<size_t>(cap, c->split_n + 1) : 0;
-    if (k) return d2h_staged(c, out, c->d_split, k * 8);
+    const uint64_t T = c->tx_on ? c->tx_T : 0;  // a text batch: the offsets without the break pieces (DS_TX_SPLIT)
+    *count = c->split_n - T + 1;
+    const size_t k = out ? std::min<size_t>(cap, *count) : 0;
+    if (k) return d2h_staged(c, out, c->tx_on ? (const uint64_t *)c->dscr[DS_TX_SPLIT] : c->d_split, k * 8);
     return 0;
 }
+
+static int encode_split_specials(bpe_gpu_ctx *c, uint64_t M, size_t n_merges, bool tx);
+static int encode_split_texts(bpe_gpu_ctx *c);
 
 int bpe_gpu_encode_split(bpe_gpu_ctx *c, const uint32_t *pairs, size_t n_merges) {
     if (!c || (!pairs && n_merges)) return BPE_GPU_EINVAL;
     if (!c->loaded) return fail(BPE_GPU_ESTATE, "encode before load");
     if (!c->split_ready) return fail(BPE_GPU_ESTATE, "encode_split: no split of the loaded bytes");
     if (n_merges > 0xFFFFFEFFull) return fail(BPE_GPU_ERANGE, "merge list too long");
-    const uint64_t M = c->sp_S ? c->sp_M : 0;
+    const bool tx = c->tx_on;
+    const uint64_t M = c->sp_S || tx ? c->sp_M : 0;
     if (M && n_merges + 256 + c->sp_S > 0xFFFFFFFFull) return fail(BPE_GPU_ERANGE, "merge list too long for the specials' ids");
     int r = encode_docs_run(c, nullptr, c->split_n, pairs, n_merges, now_ms());
-    if (r || !M) return r;
-    // The post-pass (special.hip): whichever path left ids_out / d_idoff, every special piece keeps one id,
-    // 256 + n_merges + j, and the ids and offsets after it move down.
+    if (r || (!M && !tx)) return r;
+    if (tx) c->docs_ready = false;  // (until the texts' offsets below are written)
+    if (M && (r = encode_split_specials(c, M, n_merges, tx))) return r;
+    return tx ? encode_split_texts(c) : 0;
+}
+
+// The post-pass of bpe_gpu_encode_split over the M special pieces (special.hip): whichever path left ids_out / d_idoff,
+// every special piece keeps one id, 256 + n_merges + j, and the ids and offsets after it move down.  tx: a text batch,
+// whose break pieces are among the M and keep no id.
+static int encode_split_specials(bpe_gpu_ctx *c, uint64_t M, size_t n_merges, bool tx) {
+    int r;
     const double t0 = now_ms();
     const uint64_t len = c->ids_len, ndocs = c->split_n;
     uint64_t *ist, *rem, *rsum;
     if ((r = dscratch(c, DS_SP_FIRST_ID, M * 8, &ist)) || (r = dscratch(c, DS_SP_REMOVED, (M + 1) * 8, &rem)) ||
         (r = dscratch(c, DS_SP_REMOVED_SCAN, (M + 1) * 8, &rsum)))
         return r;
-    k_sp_idlen<<<sx_grid(M + 1), SX_T, 0, c->st>>>(c->d_sp_pieces, (uint32_t)M, c->d_idoff, ist, rem);
+    k_sp_idlen<<<sx_grid(M + 1), SX_T, 0, c->st>>>(c->d_sp_pieces, (uint32_t)M, c->d_idoff, ist, rem, tx);
     HIPCHK(hipGetLastError());
     r = ROCPRIM_RUN(c, DS_SP_TMP, rocprim::exclusive_scan(tmp, tb, rem, rsum, (uint64_t)0, M + 1, rocprim::plus<uint64_t>(), c->st));
     if (r) return r;
     uint64_t removed = 0;
     HIPCHK(hipMemcpyAsync(&removed, rsum + M, 8, hipMemcpyDeviceToHost, c->st));
     HIPCHK(hipStreamSynchronize(c->st));
-    if (removed > len || len - removed < M) return fail(BPE_GPU_EINTERNAL, "encode_split: the special pieces hold more ids than there are");
+    if (removed > len || len - removed < M - (tx ? c->tx_T : 0)) return fail(BPE_GPU_EINTERNAL, "encode_split: the special pieces hold more ids than there are");
     uint32_t *ids2;
     uint64_t *idoff2;
     if ((r = dalloc(c, &ids2, len - removed, false)) || (r = dalloc(c, &idoff2, ndocs + 1, false))) return r;
     k_sp_ids<<<sx_grid(len), SX_T, 0, c->st>>>(c->h.ids_out, len, c->d_sp_pieces, (uint32_t)M, ist, rsum,
-                                              (uint32_t)(256 + n_merges), ids2);
+                                              (uint32_t)(256 + n_merges), ids2, tx);
     HIPCHK(hipGetLastError());
     k_sp_idoff<<<sx_grid(ndocs + 1), SX_T, 0, c->st>>>(c->d_idoff, ndocs, c->d_sp_pieces, (uint32_t)M, rsum, idoff2);
     HIPCHK(hipGetLastError());
@@ -365,6 +421,30 @@ int bpe_gpu_encode_split(bpe_gpu_ctx *c, const uint32_t *pairs, size_t n_merges)
     const double ms = now_ms() - t0;
     c->stats.n_out = c->ids_len;
     c->stats.occurrences = c->n0 - std::min<uint64_t>(c->n0, c->ids_len);
+    c->stats.ms_train += ms;
+    c->stats.ms_total += ms;
+    return 0;
+}
+
+// ... and of a text batch after it (texts.hip): text_off from where the break pieces' ids vanished, and the id offsets
+// without the break pieces
+static int encode_split_texts(bpe_gpu_ctx *c) {
+    const double t0 = now_ms();
+    const uint64_t T = c->tx_T, P = c->split_n;
+    const uint64_t *bpiece = (const uint64_t *)c->dscr[DS_TX_PIECE];
+    uint64_t *toff, *idoff3;
+    int r;
+    if ((r = dscratch(c, DS_TX_IDOFF, (T + 1) * 8, &toff)) || (r = dalloc(c, &idoff3, P - T + 1, false))) return r;
+    k_text_off<<<sx_grid(T + 1), SX_T, 0, c->st>>>(c->d_idoff, bpiece, T, toff);
+    HIPCHK(hipGetLastError());
+    k_text_compact<<<sx_grid(P + 1), SX_T, 0, c->st>>>(c->d_idoff, P, bpiece, T, 0, idoff3);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->st));
+    c->d_idoff = idoff3;
+    c->docs_n = P - T;
+    c->docs_info[0] = P - T;
+    c->docs_ready = true;
+    const double ms = now_ms() - t0;
     c->stats.ms_train += ms;
     c->stats.ms_total += ms;
     return 0;
@@ -465,6 +545,7 @@ static int ts_piece_table(bpe_gpu_ctx *c, uint32_t *ctl, TsTable *out) {
 int bpe_gpu_train_split(bpe_gpu_ctx *c, long max_merges, size_t *n_merges) {
     if (!c || !n_merges) return BPE_GPU_EINVAL;
     if (!c->loaded) return fail(BPE_GPU_ESTATE, "train_split before load");
+    if (c->tx_on) return fail(BPE_GPU_ESTATE, "train_split: the context holds a text batch (bpe_gpu_load_texts): training on text batches is not offered");
     if (!c->split_ready) return fail(BPE_GPU_ESTATE, "train_split: no split of the loaded bytes");
     HIPCHK(hipSetDevice(c->dev));
     c->ts_ready = false;

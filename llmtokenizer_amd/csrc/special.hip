@@ -44,8 +44,10 @@ constexpr uint32_t SX_MAX = 256;  // specials at most (BPE_GPU_SPECIAL_MAX_COUNT
 constexpr uint32_t SX_LEN = 64;   // bytes of a special at most (BPE_GPU_SPECIAL_MAX_LEN)
 constexpr uint32_t SX_T = 256;    // threads per workgroup of the per-match and per-id kernels
 constexpr uint32_t SX_GRID = 2048;
+constexpr uint32_t SX_BREAK = 255;  // the index of a text break in the match list (BPE_GPU_TEXT_BREAK; texts.hip): no special's
 static_assert(SX_MAX == BPE_GPU_SPECIAL_MAX_COUNT && SX_LEN == BPE_GPU_SPECIAL_MAX_LEN, "bpe_gpu.h names the limits");
 static_assert(SX_LEN == TS_DEDUP_MAX, "a special is one deduplicated entry of the piece table");
+static_assert(SX_BREAK == BPE_GPU_TEXT_BREAK && SX_BREAK == SX_MAX - 1, "bpe_gpu.h names the reserved index");
 
 // the set as the device sees it (one upload)
 struct SpSet {
@@ -276,10 +278,11 @@ __global__ __launch_bounds__(SX_T) void k_sp_pieces(const unsigned long long *__
 
 // ---------------------------------------------------------------- the encode post-pass
 
-// ist[m] = the first id of match m's piece, rem[m] = the ids it loses; rem[M] = 0 (the scan's total)
+// ist[m] = the first id of match m's piece, rem[m] = the ids it loses; rem[M] = 0 (the scan's total).
+// breaks: the list of a text batch, where an entry with the index SX_BREAK is a break piece, which keeps no id
 __global__ __launch_bounds__(SX_T) void k_sp_idlen(const unsigned long long *__restrict__ pieces, uint32_t M,
                                                    const uint64_t *__restrict__ id_off, uint64_t *__restrict__ ist,
-                                                   uint64_t *__restrict__ rem) {
+                                                   uint64_t *__restrict__ rem, int breaks) {
     for (uint64_t m = (uint64_t)blockIdx.x * SX_T + threadIdx.x; m <= M; m += (uint64_t)gridDim.x * SX_T) {
         if (m == M) {
             rem[m] = 0;
@@ -287,7 +290,8 @@ __global__ __launch_bounds__(SX_T) void k_sp_idlen(const unsigned long long *__r
         }
         const uint64_t p = pieces[m] >> 8, a = id_off[p], b = id_off[p + 1];
         ist[m] = a;
-        rem[m] = b > a ? b - a - 1 : 0;
+        if (breaks && (pieces[m] & 0xFFull) == SX_BREAK) rem[m] = b - a;
+        else rem[m] = b > a ? b - a - 1 : 0;
     }
 }
 
@@ -295,7 +299,7 @@ __global__ __launch_bounds__(SX_T) void k_sp_idlen(const unsigned long long *__r
 __global__ __launch_bounds__(SX_T) void k_sp_ids(const uint32_t *__restrict__ ids, uint64_t len,
                                                  const unsigned long long *__restrict__ pieces, uint32_t M,
                                                  const uint64_t *__restrict__ ist, const uint64_t *__restrict__ rsum,
-                                                 uint32_t base, uint32_t *__restrict__ out) {
+                                                 uint32_t base, uint32_t *__restrict__ out, int breaks) {
     for (uint64_t q = (uint64_t)blockIdx.x * SX_T + threadIdx.x; q < len; q += (uint64_t)gridDim.x * SX_T) {
         const uint64_t k = sx_lower(ist, M, q + 1, 0);  // matches whose piece begins at or before id q
         if (k == 0) {
@@ -303,6 +307,10 @@ __global__ __launch_bounds__(SX_T) void k_sp_ids(const uint32_t *__restrict__ id
             continue;
         }
         const uint64_t m = k - 1, a = ist[m], r0 = rsum[m], r1 = rsum[k];
+        if (breaks && (pieces[m] & 0xFFull) == SX_BREAK) {
+            if (q >= a + (r1 - r0)) out[q - r1] = ids[q];  // past the break piece, none of whose ids stays
+            continue;
+        }
         if (q > a + (r1 - r0)) out[q - r1] = ids[q];  // past the special piece
         else if (q == a) out[a - r0] = base + (uint32_t)(pieces[m] & 0xFFull);
     }

@@ -413,6 +413,48 @@ class Tokenizer:
         ids = e.ids()
         return (ids, e.doc_offsets(), e.split_offsets()) if return_offsets else ids
 
+    def encode_batch(self, texts, max_length=None, pad_id=None, truncation_side="right", return_tensors=None):
+        """Encode a list of texts (bytes; a str is encoded as UTF-8) in one pass, each exactly as encode() does it
+        alone: no piece, special or merge reaches from one text into the next, and an empty text has no id.
+        Without max_length: (ids, text_off), text k's ids being ids[text_off[k]:text_off[k + 1]] (text_off uint64,
+        len(texts) + 1 entries).  With max_length: (rows, lens), uint32[texts, max_length] and uint32[texts]: a
+        longer text is cut at truncation_side ("right" keeps its first ids, "left" its last), pad_id fills the row
+        behind the ids (required; any uint32, not checked against the vocabulary), lens[k] counts the ids in row
+        k.  return_tensors="pt" (with max_length): torch int32 tensors on the tokenizer's device, filled on the
+        device without fetching the ids to the host."""
+        if return_tensors not in (None, "pt"):
+            raise BpeError(f"encode_batch: return_tensors {return_tensors!r} (None or \"pt\")")
+        if max_length is None and (return_tensors is not None or pad_id is not None):
+            raise BpeError("encode_batch: pad_id and return_tensors go with max_length")
+        if max_length is not None and pad_id is None:
+            raise BpeError("encode_batch: max_length needs a pad_id")
+        if return_tensors == "pt":  # (before any work: the tensors must be possible)
+            import torch
+            if not torch.cuda.is_available():
+                # (a PyTorch-ROCm wheel carries a HIP runtime of its own; of two runtimes in a process the one loaded
+                # first owns the GPU, and this library binds to torch's only when torch was there before it)
+                raise BpeError('encode_batch: return_tensors="pt": torch sees no GPU; import torch before the first '
+                               "call into llmtokenizer_amd, so that both share one HIP runtime")
+        e, v = self._eng(), self.vocab
+        n_texts = e.load_texts(texts)
+        e.split(v.rule, v.specials or None)
+        e.encode_split(v.merges)
+        e.map_ids(v)
+        if max_length is None:
+            return e.ids(), e.text_offsets()
+        if return_tensors is None:
+            return e.pack_texts(max_length, pad_id, truncation_side)
+        out = torch.empty((n_texts, int(max_length)), dtype=torch.int32, device=torch.device("cuda", self.device))
+        return e.pack_texts(max_length, pad_id, truncation_side, out=out)
+
+    def decode_batch(self, ids, text_off):
+        """the inverse of encode_batch(texts): the list of the texts' bytes (NUL bytes dropped, as decode does)"""
+        ids = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+        off = np.ascontiguousarray(text_off, dtype=np.uint64).reshape(-1)
+        v = self.vocab
+        out, bo = self._eng().decode_docs(ids, off, v.merges, v.specials or None, vocab=v)
+        return [out[int(bo[k]):int(bo[k + 1])] for k in range(off.size - 1)]
+
     def decode(self, ids):
         """the bytes of vocabulary ids (NUL bytes dropped, as api.decode_batch does); an id the vocabulary does
         not hold raises BpeError"""
