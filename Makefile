@@ -39,6 +39,10 @@ COBJ_VOCAB := $(patsubst $(PKG)/src/%.c,$(BUILD)/%.o,$(CSRC_VOCAB) $(CSRC_VOCAB_
 # tests/asan_texts needs no model)
 CSRC_TEXTS := $(PKG)/src/bpe_texts.c
 COBJ_TEXTS := $(patsubst $(PKG)/src/%.c,$(BUILD)/%.o,$(CSRC_TEXTS))
+# token spans: src/bpe_spans.c is host code alone (the length table and the spans' definition, over
+# bpe_vocab_tables of src/bpe_vocab.c; no engine call, so tests/asan_spans needs no model)
+CSRC_SPANS := $(PKG)/src/bpe_spans.c
+COBJ_SPANS := $(patsubst $(PKG)/src/%.c,$(BUILD)/%.o,$(CSRC_SPANS))
 HIPDEPS := $(wildcard $(PKG)/csrc/*.hip $(PKG)/csrc/*.h) $(PKG)/src/bpe_split_presets.h include/bpe_gpu.h
 
 all: $(PKG)/libbpe_amd.so tools/bpe_main oracle
@@ -52,7 +56,7 @@ $(BUILD)/engine.o: $(HIPDEPS) | $(BUILD)
 $(BUILD)/%.o: $(PKG)/src/%.c $(wildcard include/*.h $(PKG)/src/*.h $(PKG)/csrc/unicode_classes.h) | $(BUILD)
 	$(CC) $(CFLAGS) -c $< -o $@
 
-$(PKG)/libbpe_amd.so: $(BUILD)/engine.o $(COBJ) $(COBJ_GPU) $(COBJ_TS) $(COBJ_SP) $(COBJ_SPECIAL) $(COBJ_VOCAB) $(COBJ_TEXTS)
+$(PKG)/libbpe_amd.so: $(BUILD)/engine.o $(COBJ) $(COBJ_GPU) $(COBJ_TS) $(COBJ_SP) $(COBJ_SPECIAL) $(COBJ_VOCAB) $(COBJ_TEXTS) $(COBJ_SPANS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -lm -ldl -lpthread
 
 tools/bpe_main: tools/bpe_main.c $(PKG)/libbpe_amd.so
@@ -155,3 +159,13 @@ tests/asan_texts/asan_texts: tests/asan_texts/asan_texts.c $(CSRC_TEXTS) $(wildc
 
 asan-texts: tests/asan_texts/asan_texts
 .PHONY: asan-texts
+
+# the token spans' host code (src/bpe_spans.c: bpe_span_lens and bpe_token_spans_host, over src/bpe_vocab.c) the
+# same way, in a stand-alone program that calls no engine function (tests/asan_spans/asan_spans.c); run by
+# tests/test_asan_spans.py
+tests/asan_spans/asan_spans: tests/asan_spans/asan_spans.c $(CSRC_SPANS) $(CSRC_VOCAB) $(wildcard include/*.h)
+	$(CC) -O1 -g -std=c11 -D_GNU_SOURCE -fno-omit-frame-pointer -fsanitize=address,undefined \
+	    -fno-sanitize-recover=undefined -Iinclude -o $@ tests/asan_spans/asan_spans.c $(CSRC_SPANS) $(CSRC_VOCAB) -lm
+
+asan-spans: tests/asan_spans/asan_spans
+.PHONY: asan-spans

@@ -160,6 +160,27 @@ int bpe_texts_gap(const uint8_t *bytes, size_t n, const uint64_t *text_off, size
 int bpe_texts_gap_range(const uint8_t *bytes, size_t n, const uint64_t *text_off, size_t T, size_t lo, size_t hi,
                         uint8_t *out);
 
+/* Token spans (bpe_gpu.h, "Token spans").  bpe_span_lens: the byte length of every token id, the table the spans
+ * are summed from: a byte 1 (NUL included), merge r the sum of its two halves, special j specials->len[j].
+ * Without a vocabulary it is indexed by internal id, *count = 256 + n_merges + specials entries; with one by
+ * vocabulary id, *count = the largest id + 1 entries and a hole 0 (bpe_vocab_tables' forward table; the
+ * vocabulary's counts must be the lists').  Two-phase: out may be NULL, at most cap entries are written.
+ * BPE_GPU_EINVAL for a merge that names an id at or above its own (its rank is in the message),
+ * BPE_GPU_ERANGE for a length above 2^32 - 1; msg (may be NULL) receives the message.  No GPU. */
+int bpe_span_lens(const uint32_t *pairs, size_t n_merges, const bpe_gpu_specials *specials, const bpe_gpu_vocab *vocab,
+                  uint32_t *out, size_t cap, size_t *count, char *msg, size_t msg_cap);
+/* The spans of ids[0 .. n_ids) held as T texts: text k has the ids [text_off[k], text_off[k + 1]) and the bytes
+ * [byte_off[k], byte_off[k + 1]) of bytes[0 .. n) (both offset arrays run from 0 to their count without
+ * falling); lens[0 .. n_lens) is bpe_span_lens' table in the ids' numbering.  out[2 i], out[2 i + 1] = the span
+ * of id i relative to its text's first byte, in bytes (unit BPE_SPAN_BYTE; bytes may be NULL) or in characters
+ * (BPE_SPAN_CHAR), as bpe_gpu.h defines them.  Plain loops: this is the definition the device is held to.
+ * BPE_GPU_EDATA for an id outside the table (or of length 0: a hole) and for a text whose lengths do not sum to
+ * its byte count (the text's index is in the message); BPE_GPU_ERANGE for a text above 2^32 - 1 bytes;
+ * BPE_GPU_EINVAL for bad offsets or another unit.  msg (may be NULL) receives the message.  No GPU. */
+int bpe_token_spans_host(const uint32_t *ids, size_t n_ids, const uint64_t *text_off, size_t T, const uint8_t *bytes,
+                         size_t n, const uint64_t *byte_off, const uint32_t *lens, size_t n_lens, int unit, uint32_t *out,
+                         char *msg, size_t msg_cap);
+
 /* statistics of the last compress/compress_ex/bpe_train_bytes/bpe_encode_bytes/bpe_encode_docs/bpe_encode_split(_preset) */
 int bpe_last_stats(bpe_gpu_stats *out);
 

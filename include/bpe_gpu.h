@@ -599,6 +599,56 @@ int bpe_gpu_fetch_text_offsets(bpe_gpu_ctx *ctx, uint64_t *out, size_t cap, size
 int bpe_gpu_pack_texts(bpe_gpu_ctx *ctx, uint32_t row_len, uint32_t pad_id, int side, uint32_t *out,
                        int out_is_device, uint32_t *lens);
 
+/* ------------------------------------------------------------------------
+ * Token spans: where in its text every resident id comes from.
+ *
+ * The contract.  For a text t (bytes) encoded to the ids x[0 .. m), token i
+ * stands for the bytes t[bs_i .. be_i) with bs_0 = 0, be_i = bs_(i + 1) and
+ * be_(m - 1) = len(t).  A token's length is fixed by its id: a byte is 1 (NUL
+ * included, unlike the decoders' table, which drops NULs), merge r the sum of its
+ * two halves, special j the length of special j.  In a text batch every text has
+ * spans of its own, relative to its own first byte; an empty text has none.
+ * Without a text batch the resident bytes are the one text.
+ *
+ * Two units.  BPE_SPAN_BYTE: (bs_i, be_i).  BPE_SPAN_CHAR: with lead(p) = the
+ * number of bytes in t[0 .. p) that are no UTF-8 continuation byte
+ * ((b & 0xC0) != 0x80), the span is (max(lead(bs_i + 1), 1) - 1, lead(be_i)).
+ * For valid UTF-8 that is the index of the code point holding the token's first
+ * byte and one past the code point holding its last, so a token that holds only
+ * a part of a character reports the whole character, as Encoding.offsets of the
+ * `tokenizers` library does (for a tokenizer.json without a post-processor;
+ * trim_offsets belongs to a ByteLevel post-processor, which is not applied).  For
+ * bytes that are no UTF-8 the formula is the definition; the max keeps a text
+ * that begins with a continuation byte at 0.  Spans are uint32 pairs.
+ *
+ * bpe_gpu_token_spans computes them on the device (spans.hip) from a length
+ * table built on the host (bpe_ex.h bpe_span_lens) and keeps them in HBM.  They
+ * live as long as the ids they describe and go where those go; a later
+ * bpe_gpu_map_ids does not touch them (numbering is not position).
+ * ---------------------------------------------------------------------- */
+#define BPE_SPAN_BYTE 0
+#define BPE_SPAN_CHAR 1
+/* The spans of the resident ids of the last bpe_gpu_encode_split / bpe_gpu_encode_docs, with or without a text
+   batch, before or after bpe_gpu_map_ids: mapped ids need `vocab` (the table is then in its numbering), unmapped
+   ids with one are BPE_GPU_ESTATE, as are mapped ids without, no such ids, and the ids of bpe_gpu_encode or a
+   training.  specials: those of the split (NULL: none).  BPE_GPU_EINVAL when n_merges is not the encode's, for
+   another unit, a list bpe_span_lens refuses or a vocabulary bpe_vocab_check refuses.  BPE_GPU_EDATA, nothing
+   kept, for an id outside the table ("spans: unknown token id") and when the lengths do not sum to the bytes of
+   the texts ("... not the merge list of this encode"); the context goes on as it was. */
+int bpe_gpu_token_spans(bpe_gpu_ctx *ctx, const uint32_t *pairs, size_t n_merges, const bpe_gpu_specials *specials,
+                        const bpe_gpu_vocab *vocab, int unit);
+/* the spans, out[2 i] and out[2 i + 1] for id i; out may be NULL, *count = the ids, at most cap spans are
+   written.  BPE_GPU_ESTATE without spans. */
+int bpe_gpu_fetch_token_spans(bpe_gpu_ctx *ctx, uint32_t *out, size_t cap, size_t *count);
+/* The spans of a text batch as rows: out[T][row_len][2] uint32, cut as bpe_gpu_pack_texts cuts the ids (the same
+   side, the same lens), the cells behind the ids (0, 0).  With side 1 the spans stay relative to the whole
+   text: they are not rebased to the cut.  out_is_device as bpe_gpu_pack_texts; a device pointer must be 8-byte
+   aligned.  Refusals as bpe_gpu_pack_texts; BPE_GPU_ESTATE without a text batch or without spans. */
+int bpe_gpu_pack_spans(bpe_gpu_ctx *ctx, uint32_t row_len, int side, uint32_t *out, int out_is_device);
+/* out4 = {ids one thread of k_spans takes per step, ids per workgroup step, ids per grid step, bytes per grid
+   step of k_span_lead} (pure function, no GPU; for the tests) */
+int bpe_gpu_span_info(uint64_t *out4);
+
 int bpe_gpu_get_stats(bpe_gpu_ctx *ctx, bpe_gpu_stats *st);
 
 /* Position-keyed checksum of the ids of the last train / encode, computed in

@@ -56,6 +56,9 @@ EXPORTS = [
     # bpe_gpu.h / bpe_ex.h: text batches
     "bpe_gpu_load_texts", "bpe_gpu_fetch_text_offsets", "bpe_gpu_pack_texts", "bpe_texts_check", "bpe_texts_gap",
     "bpe_texts_gap_range",
+    # bpe_gpu.h / bpe_ex.h: token spans
+    "bpe_gpu_token_spans", "bpe_gpu_fetch_token_spans", "bpe_gpu_pack_spans", "bpe_gpu_span_info", "bpe_span_lens",
+    "bpe_token_spans_host",
 ]
 
 
@@ -273,6 +276,12 @@ def load():
     L.bpe_texts_check.argtypes = [vp, sz, sz, ctypes.c_char_p, sz]
     L.bpe_texts_gap.argtypes = [vp, sz, vp, sz, vp, sz]
     L.bpe_texts_gap_range.argtypes = [vp, sz, vp, sz, sz, sz, vp]
+    L.bpe_gpu_token_spans.argtypes = [vp, vp, sz, spp, vop, ctypes.c_int]
+    L.bpe_gpu_fetch_token_spans.argtypes = [vp, vp, sz, ctypes.POINTER(sz)]
+    L.bpe_gpu_pack_spans.argtypes = [vp, ctypes.c_uint32, ctypes.c_int, vp, ctypes.c_int]
+    L.bpe_gpu_span_info.argtypes = [vp]
+    L.bpe_span_lens.argtypes = [vp, sz, spp, vop, vp, sz, ctypes.POINTER(sz), ctypes.c_char_p, sz]
+    L.bpe_token_spans_host.argtypes = [vp, sz, vp, sz, vp, sz, vp, vp, sz, ctypes.c_int, vp, ctypes.c_char_p, sz]
     L.bpe_release_engines.argtypes = []
     L.bpe_release_engines.restype = None
     _LIB = L

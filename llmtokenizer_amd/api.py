@@ -505,6 +505,76 @@ def texts_gap(data, text_off, lo=None, hi=None):
     return out.tobytes()
 
 
+SPAN_UNITS = {"byte": 0, "char": 1}  # bpe_gpu.h BPE_SPAN_BYTE, BPE_SPAN_CHAR
+
+
+def _span_unit(unit, what):
+    if unit not in SPAN_UNITS:
+        raise BpeError(f"{what}: unit {unit!r} (have {sorted(SPAN_UNITS)})")
+    return SPAN_UNITS[unit]
+
+
+def _span_args(merges, specials, vocab):
+    """(pairs pointer, merges, specials ref or None, vocabulary ref or None, the objects to keep) for the span calls"""
+    m = np.ascontiguousarray(merges, dtype=np.uint32).reshape(-1)
+    sp = check_specials(specials) if specials else None
+    cv = vocab.c_vocab() if vocab is not None else None
+    return (m.ctypes.data_as(ctypes.c_void_p) if m.size else None, m.size // 2, sp.ref if sp else None,
+            cv.ref if cv else None, (m, sp, cv))
+
+
+def span_lens(merges, specials=None, vocab=None):
+    """The byte length of every token id (bpe_ex.h bpe_span_lens), uint32: a byte is 1 (NUL included), merge r the sum
+    of its halves, special j len(specials[j]).  Indexed by internal id (256 + merges + specials entries) or, with
+    vocab (a vocab.Vocab over the same merges and specials), by vocabulary id (vocab.size entries, a hole 0).  A
+    merge that names an id at or above its own raises BpeError with its rank.  No GPU."""
+    L = _lib.load()
+    pairs, k, sp, cv, keep = _span_args(merges, specials, vocab)
+    n = ctypes.c_size_t(0)
+    msg = ctypes.create_string_buffer(400)
+    rc = L.bpe_span_lens(pairs, k, sp, cv, None, 0, ctypes.byref(n), msg, len(msg))
+    out = np.zeros(n.value if not rc else 0, dtype=np.uint32)
+    if not rc:
+        rc = L.bpe_span_lens(pairs, k, sp, cv, out.ctypes.data_as(ctypes.c_void_p), out.size, ctypes.byref(n), msg, len(msg))
+    if rc:
+        raise BpeError(f"span_lens: {L.bpe_gpu_strerror(rc).decode()} ({msg.value.decode(errors='replace')})")
+    return out
+
+
+def token_spans_host(ids, text_off, data, byte_off, lens, unit="byte"):
+    """The spans of ids held as texts, on the host in plain loops (bpe_ex.h bpe_token_spans_host: the definition
+    Engine.token_spans is held to): text k has the ids [text_off[k], text_off[k + 1]) and the bytes
+    [byte_off[k], byte_off[k + 1]) of data; lens is span_lens' table in the ids' numbering.  Returns uint32[n, 2],
+    each span relative to its text's first byte, in bytes or (unit "char") characters.  An id outside the table and
+    a text whose lengths do not sum to its bytes raise BpeError (the text's index in the message).  No GPU."""
+    L = _lib.load()
+    u = _span_unit(unit, "token_spans_host")
+    ids = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+    toff, boff = _doc_offsets(text_off), _doc_offsets(byte_off)
+    if toff.size < 1 or toff.size != boff.size:
+        raise BpeError("token_spans_host: text_off and byte_off must both hold texts + 1 entries")
+    buf = np.frombuffer(bytes(data), dtype=np.uint8)
+    lens = np.ascontiguousarray(lens, dtype=np.uint32).reshape(-1)
+    out = np.zeros((ids.size, 2), dtype=np.uint32)
+    msg = ctypes.create_string_buffer(400)
+    vp = ctypes.c_void_p
+    rc = L.bpe_token_spans_host(ids.ctypes.data_as(vp) if ids.size else None, ids.size, toff.ctypes.data_as(vp),
+                                toff.size - 1, buf.ctypes.data_as(vp) if buf.size else None, buf.size,
+                                boff.ctypes.data_as(vp), lens.ctypes.data_as(vp) if lens.size else None, lens.size, u,
+                                out.ctypes.data_as(vp) if ids.size else None, msg, len(msg))
+    if rc:
+        raise BpeError(f"token_spans_host: {L.bpe_gpu_strerror(rc).decode()} ({msg.value.decode(errors='replace')})")
+    return out
+
+
+def span_info():
+    """{ids one thread of the span kernel takes per step, ids per workgroup step, ids per grid step, bytes per grid
+    step of the character pass} (bpe_gpu_span_info; no GPU; for the tests)"""
+    out = np.zeros(4, dtype=np.uint64)
+    _lib.check(_lib.load().bpe_gpu_span_info(out.ctypes.data_as(ctypes.c_void_p)), "span_info")
+    return {"per_thread": int(out[0]), "per_block": int(out[1]), "per_grid": int(out[2]), "lead_bytes_per_grid": int(out[3])}
+
+
 PACK_SIDES = {"right": 0, "left": 1}  # the side a longer text is cut at: "right" keeps its first ids, "left" its last
 
 
@@ -590,6 +660,50 @@ class Engine:
                                              vp(out.data_ptr()) if out.numel() else None, 1,
                                              vp(lens.data_ptr()) if T else None), "pack_texts")
         return out, lens
+
+    def token_spans(self, merges, specials=None, vocab=None, unit="byte"):
+        """the span of every resident id of the last encode_split() / encode_docs() in its text, uint32[n, 2]
+        (bpe_gpu_token_spans, computed and kept on the device): in bytes, or with unit "char" in characters as
+        `tokenizers`' Encoding.offsets counts them (bpe_gpu.h, "Token spans").  In a text batch every span is
+        relative to its own text.  merges / specials: those of the encode and the split; vocab: needed after
+        map_ids(), refused before it.  A list that is not the encode's raises BpeError (BPE_GPU_EINVAL for another
+        count, BPE_GPU_EDATA when the lengths do not sum to the text) and the engine goes on."""
+        u = _span_unit(unit, "token_spans")
+        pairs, k, sp, cv, keep = _span_args(merges, specials, vocab)
+        _lib.check(self.L.bpe_gpu_token_spans(self.ctx, pairs, k, sp, cv, u), "token_spans")
+        n = ctypes.c_size_t(0)
+        _lib.check(self.L.bpe_gpu_fetch_token_spans(self.ctx, None, 0, ctypes.byref(n)), "fetch_token_spans")
+        out = np.zeros((n.value, 2), dtype=np.uint32)
+        if n.value:
+            _lib.check(self.L.bpe_gpu_fetch_token_spans(self.ctx, out.ctypes.data_as(ctypes.c_void_p), n.value,
+                                                        ctypes.byref(n)), "fetch_token_spans")
+        return out
+
+    def pack_spans(self, row_len, side="right", out=None):
+        """the spans of the last token_spans() over a text batch as rows, uint32[texts, row_len, 2]
+        (bpe_gpu_pack_spans): cut as pack_texts(row_len, ., side) cuts the ids, the cells behind the ids (0, 0); with
+        side "left" the spans stay relative to the whole text.  out: a contiguous torch tensor of 32-bit integers,
+        [texts, row_len, 2], on this engine's device: written on the device and returned."""
+        if side not in PACK_SIDES:
+            raise BpeError(f"pack_spans: side {side!r} (have {sorted(PACK_SIDES)})")
+        row_len = int(row_len)
+        if not 0 <= row_len <= 0xFFFFFFFF:
+            raise BpeError("pack_spans: row_len is a uint32")
+        T = self.text_offsets().size - 1
+        vp = ctypes.c_void_p
+        if out is None:
+            rows = np.zeros((T, row_len, 2), dtype=np.uint32)
+            _lib.check(self.L.bpe_gpu_pack_spans(self.ctx, row_len, PACK_SIDES[side],
+                                                 rows.ctypes.data_as(vp) if rows.size else None, 0), "pack_spans")
+            return rows
+        import torch
+        if (not isinstance(out, torch.Tensor) or not out.is_cuda or out.element_size() != 4 or out.is_floating_point()
+                or tuple(out.shape) != (T, row_len, 2) or not out.is_contiguous()):
+            raise BpeError(f"pack_spans: out must be a contiguous 32-bit integer tensor of shape ({T}, {row_len}, 2) on the GPU")
+        torch.cuda.current_stream(out.device).synchronize()  # (the call writes on the context's stream)
+        _lib.check(self.L.bpe_gpu_pack_spans(self.ctx, row_len, PACK_SIDES[side],
+                                             vp(out.data_ptr()) if out.numel() else None, 1), "pack_spans")
+        return out
 
     def load_file(self, path):
         """stream a file into HBM (bpe_gpu_load_fd: pinned double-buffered

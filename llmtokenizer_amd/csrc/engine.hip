@@ -32,6 +32,7 @@
 #include "special.hip"
 #include "vocab.hip"
 #include "texts.hip"
+#include "spans.hip"
 
 // (bpe_ex.h, src/bpe_texts.c: the host definition of a text batch's offsets and its resident bytes)
 extern "C" int bpe_texts_check(const uint64_t *text_off, size_t T, size_t n, char *msg, size_t msg_cap);
@@ -43,6 +44,9 @@ extern "C" int bpe_specials_check(const bpe_gpu_specials *specials, char *msg, s
 extern "C" int bpe_vocab_check(const bpe_gpu_vocab *vocab, const uint32_t *pairs, size_t n_merges, char *msg, size_t msg_cap);
 extern "C" int bpe_vocab_tables(const bpe_gpu_vocab *vocab, uint32_t *fwd, size_t fwd_cap, uint32_t *inv, size_t inv_cap,
                                 size_t *n_fwd, size_t *n_inv);
+// (bpe_ex.h, src/bpe_spans.c: the byte length of every token id)
+extern "C" int bpe_span_lens(const uint32_t *pairs, size_t n_merges, const bpe_gpu_specials *specials, const bpe_gpu_vocab *vocab,
+                             uint32_t *out, size_t cap, size_t *count, char *msg, size_t msg_cap);
 
 using namespace bpeamd;
 
@@ -308,6 +312,10 @@ struct bpe_gpu_ctx {
     bool ids_ready = false;
     uint64_t ids_len = 0;
     bool ids_mapped = false;  // bpe_gpu_map_ids made them vocabulary ids; goes with the ids (free_train)
+    // the last bpe_gpu_token_spans: scratch slot DS_SPN_OUT holds spans_n spans of the resident ids.  They go where
+    // ids_ready goes: every assignment to it clears spans_ready.
+    bool spans_ready = false;
+    uint64_t spans_n = 0;
     // the last bpe_gpu_encode_docs: id offsets (device, [docs_n + 1]) and bpe_gpu_docs_info's counters
     bool docs_ready = false;
     uint64_t docs_n = 0;
@@ -504,6 +512,7 @@ void free_train(bpe_gpu_ctx *c, bool release = false) {
     for (hipGraphExec_t g : c->retired)
         if (real_graph(g)) (void)hipGraphExecDestroy(g);
     c->retired.clear();
+    c->spans_ready = false;
     c->ids_ready = false;
     c->ids_mapped = false;
     c->docs_ready = false;
@@ -1810,6 +1819,7 @@ int compact_ids(bpe_gpu_ctx *c) {
     HIPCHK(hipMemcpyAsync(&tot, d_ticket + 1, 4, hipMemcpyDeviceToHost, c->st));
     HIPCHK(hipStreamSynchronize(c->st));
     c->ids_len = tot;
+    c->spans_ready = false;
     c->ids_ready = true;
     return 0;
 }
@@ -2401,6 +2411,7 @@ int ew_run(bpe_gpu_ctx *c, const EwPlan &P, const uint32_t *d_img, uint32_t halo
     HIPCHK(hipStreamSynchronize(c->st));
     *ok = fl == 0;
     c->ids_len = total;
+    c->spans_ready = false;
     c->ids_ready = *ok;
     c->stats.enc_windows = nwin;
     return 0;
@@ -2943,6 +2954,7 @@ int bpe_gpu_encode(bpe_gpu_ctx *c, const uint32_t *pairs, size_t n_merges) {
     if (n_merges) HIPCHK(hipMemcpyAsync(c->d_enc_pairs, pairs, n_merges * 8, hipMemcpyHostToDevice, c->st));
     if (c->n0 == 0) {
         c->ids_len = 0;
+        c->spans_ready = false;
         c->ids_ready = true;
         return 0;
     }
@@ -3527,6 +3539,7 @@ static int encode_docs_run(bpe_gpu_ctx *c, const uint64_t *doc_off, size_t ndocs
     if (getenv_int("BPE_EW_PROF", 0))  // host phases (the kernel's own: ed_run, in an EW_PROF build)
         fprintf(stderr, "encode_docs host (ms): offset check %.2f, plan %.2f, first pass + fallback %.2f\n", t0 - t_chk,
                 t_plan - t0, t1 - t_plan);
+    c->spans_ready = false;
     c->ids_ready = true;
     c->docs_ready = true;
     c->docs_n = ndocs;
@@ -3658,6 +3671,7 @@ int bpe_gpu_map_ids(bpe_gpu_ctx *c, const bpe_gpu_vocab *vocab) {
     HIPCHK(hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, c->st));
     HIPCHK(hipStreamSynchronize(c->st));
     if (err) {  // (the ids are half rewritten: they are gone)
+        c->spans_ready = false;
         c->ids_ready = false;
         c->ids_mapped = false;
         c->docs_ready = false;
@@ -3741,6 +3755,159 @@ int bpe_gpu_pack_texts(bpe_gpu_ctx *c, uint32_t row_len, uint32_t pad_id, int si
         int r;
         if ((r = d2h_staged(c, out, d_out, cells * 4))) return r;
         if (lens && (r = d2h_staged(c, lens, d_lens, T * 4))) return r;
+    }
+    HIPCHK(hipStreamSynchronize(c->st));
+    return 0;
+}
+
+// ------------------------------------------------ token spans (spans.hip; the length table: src/bpe_spans.c)
+
+int bpe_gpu_span_info(uint64_t *out4) {
+    if (!out4) return BPE_GPU_EINVAL;
+    out4[0] = 1;
+    out4[1] = SPN_T;
+    out4[2] = (uint64_t)SPN_T * SPN_GRID;
+    out4[3] = (uint64_t)SPN_LBYTES * SPN_T * SPN_LGRID;
+    return 0;
+}
+
+int bpe_gpu_token_spans(bpe_gpu_ctx *c, const uint32_t *pairs, size_t n_merges, const bpe_gpu_specials *specials,
+                        const bpe_gpu_vocab *vocab, int unit) {
+    if (!c || (!pairs && n_merges)) return BPE_GPU_EINVAL;
+    if (unit != BPE_SPAN_BYTE && unit != BPE_SPAN_CHAR) return fail(BPE_GPU_EINVAL, "spans: the unit is neither BPE_SPAN_BYTE nor BPE_SPAN_CHAR");
+    if (!c->ids_ready || !c->docs_ready) return fail(BPE_GPU_ESTATE, "spans: no ids of bpe_gpu_encode_split or bpe_gpu_encode_docs");
+    if (c->ids_mapped && !vocab) return fail(BPE_GPU_ESTATE, "spans: the resident ids are vocabulary ids: the vocabulary is needed");
+    if (!c->ids_mapped && vocab) return fail(BPE_GPU_ESTATE, "spans: a vocabulary is given, the resident ids are not mapped to one");
+    char msg[400];
+    int r;
+    if (c->ids_len && n_merges != c->stats.merges) {  // (as bpe_gpu_map_ids: no id, no list to hold it to)
+        snprintf(msg, sizeof msg, "spans: the list holds %zu merges, the ids were made with %llu", n_merges,
+                 (unsigned long long)c->stats.merges);
+        return fail(BPE_GPU_EINVAL, msg);
+    }
+    if (bpe_specials_check(specials, msg, sizeof msg)) return fail(BPE_GPU_EINVAL, msg);
+    if (vocab && (r = bpe_vocab_check(vocab, pairs, n_merges, msg, sizeof msg))) return fail(r, r == BPE_GPU_EINVAL ? msg : "spans: out of memory");
+    size_t nl = 0;
+    if ((r = bpe_span_lens(pairs, n_merges, specials, vocab, nullptr, 0, &nl, msg, sizeof msg))) return fail(r, msg);
+    std::vector<uint32_t> lens(nl);  // (lives until the synchronisation below)
+    if ((r = bpe_span_lens(pairs, n_merges, specials, vocab, lens.data(), nl, &nl, msg, sizeof msg))) return fail(r, msg);
+    HIPCHK(hipSetDevice(c->dev));
+    c->spans_ready = false;
+    const uint64_t len = c->ids_len, T = c->tx_T;
+    const bool tx = c->tx_on;
+    const uint64_t nbytes = tx ? c->n0 - T : c->n0;  // the bytes of the texts' plain join
+    const uint32_t *ids = c->h.ids_out;
+    const uint64_t *toff = tx ? (const uint64_t *)c->dscr[DS_TX_IDOFF] : nullptr;
+    const uint64_t *boff = tx ? (const uint64_t *)c->dscr[DS_TX_BOFF] : nullptr;
+    uint32_t *d_lens, *d_err;
+    uint64_t *d_start;
+    uint2 *d_out;
+    if ((r = dscratch(c, DS_SPN_LENS, nl * 4, &d_lens)) || (r = dscratch(c, DS_SPN_START, (len + 1) * 8, &d_start)) ||
+        (r = dscratch(c, DS_SPN_ERR, 64, &d_err)) || (r = dscratch(c, DS_SPN_OUT, std::max<uint64_t>(len, 1) * 8, &d_out)))
+        return r;
+    HIPCHK(hipMemcpyAsync(d_lens, lens.data(), nl * 4, hipMemcpyHostToDevice, c->st));
+    HIPCHK(hipMemsetAsync(d_err, 0, 4, c->st));
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(std::max<uint64_t>((len + SPN_T - 1) / SPN_T, 1), SPN_GRID);
+    if (len) k_span_chk<<<grid, SPN_T, 0, c->st>>>(ids, len, d_lens, (uint32_t)nl, d_err);
+    HIPCHK(hipGetLastError());
+    auto it = rocprim::make_transform_iterator(rocprim::make_counting_iterator<uint64_t>(0), SpanLen{ids, d_lens, len, (uint32_t)nl});
+    r = ROCPRIM_RUN(c, DS_SCAN_TMP, rocprim::exclusive_scan(tmp, tb, it, d_start, (uint64_t)0, len + 1, rocprim::plus<uint64_t>(), c->st));
+    if (r) return r;
+    if (tx) {
+        k_span_texts<<<(uint32_t)std::min<uint64_t>((T + SPN_T) / SPN_T, SPN_GRID), SPN_T, 0, c->st>>>(d_start, toff, boff, T, len, d_err);
+        HIPCHK(hipGetLastError());
+    }
+    uint32_t err = 0;
+    uint64_t total = 0;
+    HIPCHK(hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipMemcpyAsync(&total, d_start + len, 8, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipStreamSynchronize(c->st));
+    if (err & 1u) return fail(BPE_GPU_EDATA, "spans: unknown token id");
+    if (total != nbytes || (err & 2u)) {
+        if (total != nbytes)
+            snprintf(msg, sizeof msg, "spans: the ids' lengths sum to %llu, the text holds %llu bytes: not the merge list of this encode",
+                     (unsigned long long)total, (unsigned long long)nbytes);
+        else
+            snprintf(msg, sizeof msg, "spans: the ids' lengths sum to %llu as the texts' bytes do, but not text by text: not the merge list of this encode",
+                     (unsigned long long)total);
+        return fail(BPE_GPU_EDATA, msg);
+    }
+    const unsigned long long *d_mask = nullptr;
+    const uint32_t *d_pref = nullptr;
+    if (unit == BPE_SPAN_CHAR && len) {
+        // a word more than the bytes fill, so that lead(n0) has its word: the bytes keep 64 readable ones past n0
+        const uint64_t nwords = (c->n0 >> 6) + 1;
+        unsigned long long *mask;
+        uint32_t *cnt, *pref;
+        if ((r = dscratch(c, DS_SPN_MASK, nwords * 8, &mask)) || (r = dscratch(c, DS_SPN_CNT, nwords * 4, &cnt)) ||
+            (r = dscratch(c, DS_SPN_PREF, nwords * 4, &pref)))
+            return r;
+        const uint64_t step = (uint64_t)SPN_T, groups = nwords * 4;
+        k_span_lead<<<(uint32_t)std::min<uint64_t>((groups + step - 1) / step, SPN_LGRID), SPN_T, 0, c->st>>>(c->h.bytes, nwords, mask, cnt);
+        HIPCHK(hipGetLastError());
+        r = ROCPRIM_RUN(c, DS_SCAN_TMP, rocprim::exclusive_scan(tmp, tb, cnt, pref, (uint32_t)0, nwords, rocprim::plus<uint32_t>(), c->st));
+        if (r) return r;
+        d_mask = mask;
+        d_pref = pref;
+    }
+    if (len) k_spans<<<grid, SPN_T, 0, c->st>>>(d_start, len, toff, boff, T, d_mask, d_pref, d_out);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->st));
+    c->spans_ready = true;
+    c->spans_n = len;
+    return 0;
+}
+
+int bpe_gpu_fetch_token_spans(bpe_gpu_ctx *c, uint32_t *out, size_t cap, size_t *count) {
+    if (!c || !count) return BPE_GPU_EINVAL;
+    if (!c->ids_ready || !c->spans_ready) return fail(BPE_GPU_ESTATE, "no spans: bpe_gpu_token_spans first");
+    HIPCHK(hipSetDevice(c->dev));
+    *count = c->spans_n;
+    const size_t k = out ? std::min<size_t>(cap, c->spans_n) : 0;
+    if (k) return d2h_staged(c, out, c->dscr[DS_SPN_OUT], k * 8);
+    return 0;
+}
+
+int bpe_gpu_pack_spans(bpe_gpu_ctx *c, uint32_t row_len, int side, uint32_t *out, int out_is_device) {
+    if (!c) return BPE_GPU_EINVAL;
+    if (row_len == 0) return fail(BPE_GPU_EINVAL, "pack_spans: row_len is 0");
+    if (side != 0 && side != 1) return fail(BPE_GPU_EINVAL, "pack_spans: side is neither 0 (keep the first ids) nor 1 (the last)");
+    if (row_len > PK_ROW_MAX) return fail(BPE_GPU_ERANGE, "pack_spans: row_len above 2^24");
+    if (!c->tx_on) return fail(BPE_GPU_ESTATE, "pack_spans: the context holds no text batch (bpe_gpu_load_texts)");
+    if (!c->ids_ready || !c->docs_ready) return fail(BPE_GPU_ESTATE, "pack_spans: no ids: encode_split first");
+    if (!c->spans_ready) return fail(BPE_GPU_ESTATE, "pack_spans: no spans: bpe_gpu_token_spans first");
+    const uint64_t T = c->tx_T;
+    if (!T) return 0;
+    if (!out) return fail(BPE_GPU_EINVAL, "pack_spans: no output");
+    HIPCHK(hipSetDevice(c->dev));
+    const size_t cells = (size_t)T * row_len;
+    uint2 *d_out = (uint2 *)out;
+    if (out_is_device) {
+        hipPointerAttribute_t at;
+        if (hipPointerGetAttributes(&at, out) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != c->dev) {
+            (void)hipGetLastError();
+            return fail(BPE_GPU_EINVAL, "pack_spans: out is no device pointer of the context's device");
+        }
+        if ((uintptr_t)out & 7u) return fail(BPE_GPU_EINVAL, "pack_spans: a pointer that is not 8-byte aligned");
+    } else {
+        int r;
+        if ((r = dscratch(c, DS_SPN_PACK, cells * 8, &d_out))) return r;
+    }
+    // the workgroup's shape, as bpe_gpu_pack_texts': bx lanes along a row (a power of two, one or two cells each), by rows
+    const bool vec = row_len % 2 == 0 && ((uintptr_t)d_out & 15u) == 0;
+    const uint32_t units = vec ? row_len / 2 : row_len;
+    uint32_t bx = 1;
+    while (bx < units && bx < PK_T) bx *= 2;
+    const uint32_t by = PK_T / bx, gx = (units + bx - 1) / bx;
+    const uint32_t gy = (uint32_t)std::min<uint64_t>({(T + by - 1) / by, (uint64_t)65535, (uint64_t)std::max<uint32_t>(PK_BLOCKS / gx, 1)});
+    const uint2 *spans = (const uint2 *)c->dscr[DS_SPN_OUT];
+    const uint64_t *toff = (const uint64_t *)c->dscr[DS_TX_IDOFF];
+    if (vec) k_pack_spans<true><<<dim3(gx, gy), dim3(bx, by), 0, c->st>>>(spans, toff, T, row_len, (uint32_t)side, d_out);
+    else k_pack_spans<false><<<dim3(gx, gy), dim3(bx, by), 0, c->st>>>(spans, toff, T, row_len, (uint32_t)side, d_out);
+    HIPCHK(hipGetLastError());
+    if (!out_is_device) {
+        int r;
+        if ((r = d2h_staged(c, out, d_out, cells * 8))) return r;
     }
     HIPCHK(hipStreamSynchronize(c->st));
     return 0;

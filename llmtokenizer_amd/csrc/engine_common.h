@@ -672,6 +672,14 @@ enum DScr {
     DS_TX_SPLIT,         // split_run: the split's offsets without the break pieces, in the plain join's coordinates
     DS_TX_IDOFF,         // bpe_gpu_encode_split: text_off, the texts' id offsets [T + 1]; stays with the ids
     DS_TX_PACK,          // bpe_gpu_pack_texts: the rows and lens of a call with host pointers
+    DS_SPN_LENS,         // bpe_gpu_token_spans: the byte length of every id (bpe_span_lens' table)
+    DS_SPN_START,        // bpe_gpu_token_spans: start[i], the scanned lengths of the resident ids [ids + 1]
+    DS_SPN_MASK,         // bpe_gpu_token_spans, char unit: a bit per resident byte, set for a non-continuation byte
+    DS_SPN_CNT,          // ... the set bits per 64-byte word
+    DS_SPN_PREF,         // ... and their scan
+    DS_SPN_ERR,          // bpe_gpu_token_spans: error word
+    DS_SPN_OUT,          // bpe_gpu_token_spans: the spans [ids][2]; stays with the ids
+    DS_SPN_PACK,         // bpe_gpu_pack_spans: the rows of a call with a host pointer
     DS_COUNT
 };
 // bpe_gpu_train_split takes its eight token-sized arrays as one run of slots

@@ -400,9 +400,24 @@ class Tokenizer:
             self._engine.close()
             self._engine = None
 
-    def encode(self, data, return_offsets=False):
+    @staticmethod
+    def _spans_unit(return_spans, what):
+        if return_spans not in (None, "byte", "char"):
+            raise BpeError(f"{what}: return_spans {return_spans!r} (None, \"byte\" or \"char\")")
+        return return_spans
+
+    def _spans(self, unit):
+        v = self.vocab
+        return self._eng().token_spans(v.merges, v.specials or None, vocab=v, unit=unit)
+
+    def encode(self, data, return_offsets=False, return_spans=None):
         """uint32 vocabulary ids of data (bytes; a str is encoded as UTF-8).  return_offsets: also the id and
-        byte offsets of the pieces, as api.encode_split returns them."""
+        byte offsets of the pieces, as api.encode_split returns them.  return_spans ("byte" or "char"): also, as
+        the last element of the result, the span of every id in data, uint32[ids, 2], computed on the device: in
+        bytes, or in characters as Encoding.offsets of the `tokenizers` library counts them for a tokenizer.json
+        without a post-processor (a token that holds a part of a character reports the whole character;
+        trim_offsets belongs to a ByteLevel post-processor, which a Vocab does not apply)."""
+        unit = self._spans_unit(return_spans, "encode")
         if isinstance(data, str):
             data = data.encode("utf-8")
         e, v = self._eng(), self.vocab
@@ -411,9 +426,13 @@ class Tokenizer:
         e.encode_split(v.merges)
         e.map_ids(v)
         ids = e.ids()
-        return (ids, e.doc_offsets(), e.split_offsets()) if return_offsets else ids
+        out = (ids, e.doc_offsets(), e.split_offsets()) if return_offsets else (ids,)
+        if unit is not None:
+            out += (self._spans(unit),)
+        return out if len(out) > 1 else ids
 
-    def encode_batch(self, texts, max_length=None, pad_id=None, truncation_side="right", return_tensors=None):
+    def encode_batch(self, texts, max_length=None, pad_id=None, truncation_side="right", return_tensors=None,
+                     return_spans=None):
         """Encode a list of texts (bytes; a str is encoded as UTF-8) in one pass, each exactly as encode() does it
         alone: no piece, special or merge reaches from one text into the next, and an empty text has no id.
         Without max_length: (ids, text_off), text k's ids being ids[text_off[k]:text_off[k + 1]] (text_off uint64,
@@ -421,7 +440,13 @@ class Tokenizer:
         longer text is cut at truncation_side ("right" keeps its first ids, "left" its last), pad_id fills the row
         behind the ids (required; any uint32, not checked against the vocabulary), lens[k] counts the ids in row
         k.  return_tensors="pt" (with max_length): torch int32 tensors on the tokenizer's device, filled on the
-        device without fetching the ids to the host."""
+        device without fetching the ids to the host.  return_spans ("byte" or "char", see encode()): a third
+        element, every span relative to its own text: without max_length the spans uint32[ids, 2]; with it
+        span_rows uint32[texts, max_length, 2], cut as the rows are, (0, 0) behind the ids, and with
+        truncation_side "left" still relative to the whole text; with return_tensors="pt" a torch int32 tensor
+        filled on the device (no id and no span passes through the host; a batch with a text of 2^31 bytes or
+        more is refused, since int32 could not hold its spans)."""
+        unit = self._spans_unit(return_spans, "encode_batch")
         if return_tensors not in (None, "pt"):
             raise BpeError(f"encode_batch: return_tensors {return_tensors!r} (None or \"pt\")")
         if max_length is None and (return_tensors is not None or pad_id is not None):
@@ -435,17 +460,33 @@ class Tokenizer:
                 # first owns the GPU, and this library binds to torch's only when torch was there before it)
                 raise BpeError('encode_batch: return_tensors="pt": torch sees no GPU; import torch before the first '
                                "call into llmtokenizer_amd, so that both share one HIP runtime")
+            if unit is not None:
+                for k, t in enumerate(texts):
+                    # (a str of fewer than 2^29 characters has fewer than 2^31 bytes: only a longer one is encoded here)
+                    if len(t) >= 1 << 29 and len(t.encode("utf-8") if isinstance(t, str) else t) >= 1 << 31:
+                        raise BpeError(f'encode_batch: return_tensors="pt" with return_spans: text {k} holds 2^31 bytes '
+                                       "or more, its spans do not fit int32")
         e, v = self._eng(), self.vocab
         n_texts = e.load_texts(texts)
         e.split(v.rule, v.specials or None)
         e.encode_split(v.merges)
         e.map_ids(v)
         if max_length is None:
-            return e.ids(), e.text_offsets()
+            out = (e.ids(), e.text_offsets())
+            return out + (self._spans(unit),) if unit is not None else out
+        if unit is not None:  # (kept on the device; only the rows below fetch them)
+            pairs, k, sp, cv, keep = api._span_args(v.merges, v.specials or None, v)
+            _lib.check(e.L.bpe_gpu_token_spans(e.ctx, pairs, k, sp, cv, api.SPAN_UNITS[unit]), "token_spans")
         if return_tensors is None:
-            return e.pack_texts(max_length, pad_id, truncation_side)
-        out = torch.empty((n_texts, int(max_length)), dtype=torch.int32, device=torch.device("cuda", self.device))
-        return e.pack_texts(max_length, pad_id, truncation_side, out=out)
+            out = e.pack_texts(max_length, pad_id, truncation_side)
+            return out + (e.pack_spans(max_length, truncation_side),) if unit is not None else out
+        dev = torch.device("cuda", self.device)
+        rows = torch.empty((n_texts, int(max_length)), dtype=torch.int32, device=dev)
+        out = e.pack_texts(max_length, pad_id, truncation_side, out=rows)
+        if unit is None:
+            return out
+        span_rows = torch.empty((n_texts, int(max_length), 2), dtype=torch.int32, device=dev)
+        return out + (e.pack_spans(max_length, truncation_side, out=span_rows),)
 
     def decode_batch(self, ids, text_off):
         """the inverse of encode_batch(texts): the list of the texts' bytes (NUL bytes dropped, as decode does)"""
