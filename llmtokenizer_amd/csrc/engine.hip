@@ -357,6 +357,7 @@ struct bpe_gpu_ctx {
     uint32_t *d_enc_pairs = nullptr;
     hipGraphExec_t g_plain = nullptr, g_tracked = nullptr, g_encode = nullptr, g_batch = nullptr;
     bool hot_fallback = false;  // the hot set was given up for the level summaries
+    bool mode_entered = false;  // a run that began untracked (n0 >= TRACK_LIMIT) entered tracked iterations (STOP_MODE)
     bool cap_known = false;     // the caller gave the run a merge cap (setup_run: the dense pair table needs one)
     uint32_t relists = 0;       // byte-pair list rebuilds of the current run
     std::vector<uint64_t> events;  // run events of the current run (bpe_gpu_fetch_events)
@@ -780,6 +781,7 @@ int setup_run_body(bpe_gpu_ctx *c, uint32_t mcap, bool encode) {
     // k_stat_light's generation-tagged set (tracked corpora; ids in 22 bits)
     h.lcap = 0;
     h.lkey = h.lfirst = nullptr;
+    c->mode_entered = false;  // (a run that starts at n0 >= TRACK_LIMIT gets the set at its STOP_MODE, drive())
     if (!encode && !c->sharded && !c->fast && n0 < TRACK_LIMIT && h.vcap <= (1u << 22) && h.track_ub != 0) {
         h.lcap = pow2_at_least(std::max<uint64_t>(1024, 2 * n0));
         if ((r = dalloc(c, &h.lkey, h.lcap))) return r;                // generation 0: empty
@@ -1026,7 +1028,9 @@ void launch_iteration(bpe_gpu_ctx *c, bool tracked) {
         // fused speculative graph: entered with the current merge applied
         // (by the previous k_fused, or the host after a stop)
         // + the track block and the light blocks (tracked corpora)
-        const uint32_t trk = c->h.track_ub == 1 && !c->fast && c->n0 < TRACK_LIMIT ? 1 + (c->h.lcap ? LIGHT_B : 0) : 0;
+        // (a run that began untracked captures the graph again once it has entered them)
+        const uint32_t trk = c->h.track_ub == 1 && !c->fast && (c->n0 < TRACK_LIMIT || c->mode_entered)
+                                 ? 1 + (c->h.lcap ? LIGHT_B : 0) : 0;
         k_rescan_spec<<<SPEC_RB + SPEC_SB + trk, SCAN_T, 0, c->st>>>(c->dE, c->dC, SPEC_RB, trk);
         // (the hot set needs no level-2 pass; a fall-back recaptures the graph)
         if (c->h.hcap / L1W > SELECT_L1_MAX && !c->h.hot) k_rescan2<<<RESCAN2_BLOCKS, 256, 0, c->st>>>(c->dE, c->dC);
@@ -1588,6 +1592,22 @@ int drive(bpe_gpu_ctx *c, bool encode, uint32_t n_enc) {
             } else if (c->h.batch) {  // (the hot set stays; batches are for untracked iterations)
                 c->h.batch = 0;
                 if ((r = push_desc(c))) return r;
+            }
+            // The run began untracked (n0 >= TRACK_LIMIT): its fused graph was captured without the
+            // track block and setup_run gave it no light set.  Without them no phase after this one
+            // would update the per-thread table sizes, and the tie events below DYN_LIMIT would be
+            // resolved from the sizes of this first exact pass.
+            if (!c->mode_entered) {
+                c->mode_entered = true;
+                if (!c->sharded && !c->h.lcap && c->h.vcap <= (1u << 22) && c->h.track_ub != 0) {
+                    c->h.lcap = pow2_at_least(std::max<uint64_t>(1024, 2 * C.n_live));
+                    if ((r = dalloc(c, &c->h.lkey, c->h.lcap))) return r;  // generation 0: empty
+                    if ((r = dalloc(c, &c->h.lfirst, c->h.lcap, false))) return r;
+                    HIPCHK(hipMemsetAsync(c->h.lfirst, 0xFF, c->h.lcap * 8, c->st));
+                    if ((r = push_desc(c))) return r;
+                }
+                if (c->g_plain) c->retired.push_back(c->g_plain);  // captured again with the track block
+                c->g_plain = nullptr;
             }
             if ((r = push_ctl(c))) return r;
             launch_stats(c);
