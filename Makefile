@@ -43,6 +43,10 @@ COBJ_TEXTS := $(patsubst $(PKG)/src/%.c,$(BUILD)/%.o,$(CSRC_TEXTS))
 # bpe_vocab_tables of src/bpe_vocab.c; no engine call, so tests/asan_spans needs no model)
 CSRC_SPANS := $(PKG)/src/bpe_spans.c
 COBJ_SPANS := $(patsubst $(PKG)/src/%.c,$(BUILD)/%.o,$(CSRC_SPANS))
+# packed streams: src/bpe_stream.c is host code alone (the description's check and the rows' definition; no engine
+# call, so tests/asan_stream needs no model)
+CSRC_STREAM := $(PKG)/src/bpe_stream.c
+COBJ_STREAM := $(patsubst $(PKG)/src/%.c,$(BUILD)/%.o,$(CSRC_STREAM))
 HIPDEPS := $(wildcard $(PKG)/csrc/*.hip $(PKG)/csrc/*.h) $(PKG)/src/bpe_split_presets.h include/bpe_gpu.h
 
 all: $(PKG)/libbpe_amd.so tools/bpe_main oracle
@@ -56,7 +60,7 @@ $(BUILD)/engine.o: $(HIPDEPS) | $(BUILD)
 $(BUILD)/%.o: $(PKG)/src/%.c $(wildcard include/*.h $(PKG)/src/*.h $(PKG)/csrc/unicode_classes.h) | $(BUILD)
 	$(CC) $(CFLAGS) -c $< -o $@
 
-$(PKG)/libbpe_amd.so: $(BUILD)/engine.o $(COBJ) $(COBJ_GPU) $(COBJ_TS) $(COBJ_SP) $(COBJ_SPECIAL) $(COBJ_VOCAB) $(COBJ_TEXTS) $(COBJ_SPANS)
+$(PKG)/libbpe_amd.so: $(BUILD)/engine.o $(COBJ) $(COBJ_GPU) $(COBJ_TS) $(COBJ_SP) $(COBJ_SPECIAL) $(COBJ_VOCAB) $(COBJ_TEXTS) $(COBJ_SPANS) $(COBJ_STREAM)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -lm -ldl -lpthread
 
 tools/bpe_main: tools/bpe_main.c $(PKG)/libbpe_amd.so
@@ -169,3 +173,12 @@ tests/asan_spans/asan_spans: tests/asan_spans/asan_spans.c $(CSRC_SPANS) $(CSRC_
 
 asan-spans: tests/asan_spans/asan_spans
 .PHONY: asan-spans
+
+# the packed streams' host code (src/bpe_stream.c: bpe_stream_check and bpe_pack_stream_host) the same way, in a
+# stand-alone program that calls no engine function (tests/asan_stream/asan_stream.c); run by tests/test_asan_stream.py
+tests/asan_stream/asan_stream: tests/asan_stream/asan_stream.c $(CSRC_STREAM) $(wildcard include/*.h)
+	$(CC) -O1 -g -std=c11 -D_GNU_SOURCE -fno-omit-frame-pointer -fsanitize=address,undefined \
+	    -fno-sanitize-recover=undefined -Iinclude -o $@ tests/asan_stream/asan_stream.c $(CSRC_STREAM) -lm
+
+asan-stream: tests/asan_stream/asan_stream
+.PHONY: asan-stream

@@ -181,6 +181,19 @@ int bpe_token_spans_host(const uint32_t *ids, size_t n_ids, const uint64_t *text
                          size_t n, const uint64_t *byte_off, const uint32_t *lens, size_t n_lens, int unit, uint32_t *out,
                          char *msg, size_t msg_cap);
 
+/* Packed streams (bpe_gpu.h, "Packed streams").  bpe_stream_check: 0 for a description bpe_gpu_pack_stream takes;
+ * BPE_GPU_EINVAL for s == NULL, seq_len == 0 or a flag bit that is none of BPE_STREAM_BOS, _EOS and _DROP_LAST,
+ * BPE_GPU_ERANGE for seq_len above 2^24; msg (may be NULL) receives a message that names the field.  No GPU. */
+int bpe_stream_check(const bpe_gpu_stream *s, char *msg, size_t msg_cap);
+/* The rows of ids[0 .. n) held as T texts (text k has the ids [text_off[k], text_off[k + 1]); the offsets run from 0
+ * to n without falling): rows[R][seq_len], and seg and pos of the same shape unless NULL, as bpe_gpu.h defines them.
+ * Plain loops, text by text and cell by cell: this is the definition the device is held to.  *n_rows = R and
+ * *n_stream = N (each may be NULL); with rows == NULL nothing else happens.  BPE_GPU_EINVAL for rows_cap < R and for
+ * bad offsets, and what bpe_stream_check refuses.  No GPU. */
+int bpe_pack_stream_host(const uint32_t *ids, size_t n, const uint64_t *text_off, size_t T, const bpe_gpu_stream *s,
+                         uint32_t *rows, uint32_t *seg, uint32_t *pos, size_t rows_cap, size_t *n_rows,
+                         uint64_t *n_stream);
+
 /* statistics of the last compress/compress_ex/bpe_train_bytes/bpe_encode_bytes/bpe_encode_docs/bpe_encode_split(_preset) */
 int bpe_last_stats(bpe_gpu_stats *out);
 

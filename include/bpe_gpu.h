@@ -649,6 +649,63 @@ int bpe_gpu_pack_spans(bpe_gpu_ctx *ctx, uint32_t row_len, int side, uint32_t *o
    step of k_span_lead} (pure function, no GPU; for the tests) */
 int bpe_gpu_span_info(uint64_t *out4);
 
+/* ------------------------------------------------------------------------
+ * Packed streams: a text batch's ids as training rows.
+ *
+ * The contract.  Given the resident ids x[0 .. n) of a text batch (mapped or
+ * not), their text_off[0 .. T], a row length L (1 <= L <= 2^24), an optional BOS
+ * id and an optional EOS id (any uint32, not checked against a vocabulary), a pad
+ * id and a drop_last flag; b = 1 with a BOS, else 0, e the same for the EOS,
+ * w = b + e.
+ *
+ * The stream: for k = 0 .. T - 1 in order, [bos] if b, then
+ * x[text_off[k] .. text_off[k + 1]), then [eos] if e.  An empty text contributes
+ * its BOS and EOS like any other; with w == 0 it contributes nothing.  Text k
+ * starts at stream position S[k] = text_off[k] + k w, and the stream has
+ * N = n + T w cells.
+ *
+ * The rows: R = N / L, rounded down with drop_last and up without (so R == 0
+ * when N == 0, and with drop_last when N < L).  For cell c = r L + col:
+ *   rows[c] = stream[c] for c < N, else pad_id;
+ *   seg[c]  = k, the index of cell c's text in the batch, for c < N, else
+ *             BPE_STREAM_NO_TEXT (0xFFFFFFFF);
+ *   pos[c]  = c - max(S[k], r L) for c < N, else 0: it counts from the text's
+ *             first cell (its BOS if there is one) or, for a text that began in
+ *             an earlier row, from the row's first cell, so the cells of one seg
+ *             value inside one row count 0, 1, 2, ...
+ * Nothing is truncated and only the last row holds pad cells.  seg (for a
+ * block-diagonal attention mask) and pos (for position ids) are optional.
+ *
+ * bpe_gpu_pack_stream computes the rows on the device (stream.hip) from what
+ * bpe_gpu_encode_split left resident: text_off is a prefix sum already, so S has
+ * the closed form above and no scan runs.  bpe_ex.h bpe_pack_stream_host is the
+ * same in plain loops.
+ * ---------------------------------------------------------------------- */
+#define BPE_STREAM_BOS 1u        /* flags: bos_id opens every text */
+#define BPE_STREAM_EOS 2u        /* ... eos_id closes every text */
+#define BPE_STREAM_DROP_LAST 4u  /* ... a last row that the stream does not fill is dropped, not padded */
+#define BPE_STREAM_FLAGS 7u
+#define BPE_STREAM_SEQ_MAX (1u << 24)
+#define BPE_STREAM_NO_TEXT 0xFFFFFFFFu
+typedef struct {
+    uint32_t seq_len, flags, bos_id, eos_id, pad_id;
+} bpe_gpu_stream;
+/* The rows of the resident text batch: rows[R][seq_len] uint32, and seg and pos of the same shape unless NULL.
+   rows == NULL is the query: *n_rows = R and *n_stream = N are reported and nothing is launched (both may be
+   NULL).  rows_cap: the rows that rows, seg and pos each have room for.  out_is_device as bpe_gpu_pack_texts:
+   != 0: device pointers on the context's device, written on the context's stream, which is synchronised before
+   the call returns; else host memory, filled through a device buffer.
+   BPE_GPU_EINVAL for seq_len == 0, an unknown flag bit, rows_cap < R, a device pointer that is none of the
+   context's device or not 4-byte aligned; BPE_GPU_ERANGE for seq_len above 2^24; BPE_GPU_ESTATE without a text
+   batch or without its ids.  The message names the cause, and the context goes on working. */
+int bpe_gpu_pack_stream(bpe_gpu_ctx *ctx, const bpe_gpu_stream *s, uint32_t *rows, uint32_t *seg, uint32_t *pos,
+                        int out_is_device, size_t rows_cap, size_t *n_rows, uint64_t *n_stream);
+/* out4 = {cells one lane of k_pack_stream<true> takes per step, cells per workgroup step (a tile), cells the largest
+   grid takes in one step (past that many cells a workgroup takes several consecutive tiles), texts a lane walks
+   forward before it searches for itself}; k_pack_stream<false> takes a quarter of the first three (pure function,
+   no GPU; for the tests) */
+int bpe_gpu_stream_info(uint64_t *out4);
+
 int bpe_gpu_get_stats(bpe_gpu_ctx *ctx, bpe_gpu_stats *st);
 
 /* Position-keyed checksum of the ids of the last train / encode, computed in

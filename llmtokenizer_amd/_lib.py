@@ -59,6 +59,8 @@ EXPORTS = [
     # bpe_gpu.h / bpe_ex.h: token spans
     "bpe_gpu_token_spans", "bpe_gpu_fetch_token_spans", "bpe_gpu_pack_spans", "bpe_gpu_span_info", "bpe_span_lens",
     "bpe_token_spans_host",
+    # bpe_gpu.h / bpe_ex.h: packed streams
+    "bpe_gpu_pack_stream", "bpe_gpu_stream_info", "bpe_stream_check", "bpe_pack_stream_host",
 ]
 
 
@@ -71,6 +73,11 @@ class VocabIds(ctypes.Structure):
     """bpe_gpu.h bpe_gpu_vocab"""
     _fields_ = [("byte_id", ctypes.c_void_p), ("merge_id", ctypes.c_void_p), ("special_id", ctypes.c_void_p),
                 ("n_merges", ctypes.c_size_t), ("n_specials", ctypes.c_size_t)]
+
+
+class Stream(ctypes.Structure):
+    """bpe_gpu.h bpe_gpu_stream"""
+    _fields_ = [(n, ctypes.c_uint32) for n in ("seq_len", "flags", "bos_id", "eos_id", "pad_id")]
 
 
 class GpuStats(ctypes.Structure):
@@ -282,6 +289,11 @@ def load():
     L.bpe_gpu_span_info.argtypes = [vp]
     L.bpe_span_lens.argtypes = [vp, sz, spp, vop, vp, sz, ctypes.POINTER(sz), ctypes.c_char_p, sz]
     L.bpe_token_spans_host.argtypes = [vp, sz, vp, sz, vp, sz, vp, vp, sz, ctypes.c_int, vp, ctypes.c_char_p, sz]
+    stp = ctypes.POINTER(Stream)
+    L.bpe_gpu_pack_stream.argtypes = [vp, stp, vp, vp, vp, ctypes.c_int, sz, ctypes.POINTER(sz), u64p]
+    L.bpe_gpu_stream_info.argtypes = [vp]
+    L.bpe_stream_check.argtypes = [stp, ctypes.c_char_p, sz]
+    L.bpe_pack_stream_host.argtypes = [vp, sz, vp, sz, stp, vp, vp, vp, sz, ctypes.POINTER(sz), u64p]
     L.bpe_release_engines.argtypes = []
     L.bpe_release_engines.restype = None
     _LIB = L

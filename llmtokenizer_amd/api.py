@@ -575,6 +575,65 @@ def span_info():
     return {"per_thread": int(out[0]), "per_block": int(out[1]), "per_grid": int(out[2]), "lead_bytes_per_grid": int(out[3])}
 
 
+STREAM_BOS, STREAM_EOS, STREAM_DROP_LAST = 1, 2, 4  # bpe_gpu.h BPE_STREAM_*
+STREAM_NO_TEXT = 0xFFFFFFFF  # seg of a pad cell (BPE_STREAM_NO_TEXT)
+
+
+def check_stream(seq_len, pad_id=0, bos_id=None, eos_id=None, drop_last=False, flags=None):
+    """The description of a packed stream (bpe_gpu.h bpe_gpu_stream) that the packing calls take, checked by
+    bpe_ex.h bpe_stream_check: seq_len in 1 .. 2^24, the ids any uint32 (None: no BOS / EOS).  flags (for the tests):
+    the flag word as it is, in place of the one the arguments make.  Raises BpeError with the code's text and a
+    message that names the field.  No GPU."""
+    L = _lib.load()
+    vals = [int(seq_len), int(pad_id), int(bos_id or 0), int(eos_id or 0)]
+    f = (STREAM_BOS if bos_id is not None else 0) | (STREAM_EOS if eos_id is not None else 0) | \
+        (STREAM_DROP_LAST if drop_last else 0) if flags is None else int(flags)
+    if any(not 0 <= v <= 0xFFFFFFFF for v in vals + [f]):
+        raise BpeError("stream: seq_len, pad_id, bos_id, eos_id and flags are uint32")
+    s = _lib.Stream(vals[0], f, vals[2], vals[3], vals[1])
+    msg = ctypes.create_string_buffer(400)
+    rc = L.bpe_stream_check(ctypes.byref(s), msg, len(msg))
+    if rc:
+        raise BpeError(f"check_stream: {L.bpe_gpu_strerror(rc).decode()} ({msg.value.decode(errors='replace')})")
+    return s
+
+
+def pack_stream_host(ids, text_off, seq_len, pad_id, bos_id=None, eos_id=None, drop_last=False):
+    """The training rows of ids held as texts, on the host in plain loops (bpe_ex.h bpe_pack_stream_host: the
+    definition Engine.pack_stream is held to; the contract: bpe_gpu.h, "Packed streams"): every text wrapped in
+    bos_id / eos_id (None: without), the texts joined end to end and cut into rows of seq_len ids, the last row
+    filled with pad_id or, with drop_last, dropped unless full.  Returns (rows, seg, pos, N): uint32[R, seq_len]
+    each, seg the text of every cell (0xFFFFFFFF in a pad cell), pos its position in that text's stretch of the row,
+    N the cells of the stream.  No GPU."""
+    L = _lib.load()
+    s = check_stream(seq_len, pad_id, bos_id, eos_id, drop_last)
+    ids = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+    toff = _doc_offsets(text_off)
+    if toff.size < 1:
+        raise BpeError("pack_stream_host: text_off must hold texts + 1 entries")
+    vp = ctypes.c_void_p
+    R, N = ctypes.c_size_t(0), ctypes.c_uint64(0)
+    args = (ids.ctypes.data_as(vp) if ids.size else None, ids.size, toff.ctypes.data_as(vp), toff.size - 1, ctypes.byref(s))
+    rc = L.bpe_pack_stream_host(*args, None, None, None, 0, ctypes.byref(R), ctypes.byref(N))
+    if rc:  # (the description passed check_stream: what is left are the offsets)
+        raise BpeError(f"pack_stream_host: {L.bpe_gpu_strerror(rc).decode()} (text_off must run from 0 to the number "
+                       "of ids without falling)")
+    rows, seg, pos = (np.zeros((R.value, s.seq_len), dtype=np.uint32) for _ in range(3))
+    if R.value:
+        _lib.check(L.bpe_pack_stream_host(*args, rows.ctypes.data_as(vp), seg.ctypes.data_as(vp), pos.ctypes.data_as(vp),
+                                          R.value, ctypes.byref(R), ctypes.byref(N)), "pack_stream_host")
+    return rows, seg, pos, int(N.value)
+
+
+def stream_info():
+    """{cells one lane of the four-cell packing kernel takes per step, cells per workgroup step, cells the largest grid
+    takes in one step (past that many a workgroup takes several consecutive steps), texts a lane walks forward before
+    it searches for itself} (bpe_gpu_stream_info; no GPU; for the tests)"""
+    out = np.zeros(4, dtype=np.uint64)
+    _lib.check(_lib.load().bpe_gpu_stream_info(out.ctypes.data_as(ctypes.c_void_p)), "stream_info")
+    return {"per_thread": int(out[0]), "per_block": int(out[1]), "per_grid": int(out[2]), "walk": int(out[3])}
+
+
 PACK_SIDES = {"right": 0, "left": 1}  # the side a longer text is cut at: "right" keeps its first ids, "left" its last
 
 
@@ -704,6 +763,57 @@ class Engine:
         _lib.check(self.L.bpe_gpu_pack_spans(self.ctx, row_len, PACK_SIDES[side],
                                              vp(out.data_ptr()) if out.numel() else None, 1), "pack_spans")
         return out
+
+    def stream_rows(self, seq_len, bos_id=None, eos_id=None, drop_last=False):
+        """(R, N) of pack_stream() with these arguments: the rows, and the cells of the stream (the query of
+        bpe_gpu_pack_stream; nothing is launched)"""
+        s = check_stream(seq_len, 0, bos_id, eos_id, drop_last)
+        R, N = ctypes.c_size_t(0), ctypes.c_uint64(0)
+        _lib.check(self.L.bpe_gpu_pack_stream(self.ctx, ctypes.byref(s), None, None, None, 0, 0, ctypes.byref(R),
+                                              ctypes.byref(N)), "pack_stream")
+        return int(R.value), int(N.value)
+
+    def pack_stream(self, seq_len, pad_id, bos_id=None, eos_id=None, drop_last=False, segments=False, positions=False,
+                    out=None):
+        """the resident ids of a text batch (mapped or not) as training rows (bpe_gpu_pack_stream; the contract:
+        bpe_gpu.h, "Packed streams"): every text wrapped in bos_id / eos_id (any uint32; None: without), the texts
+        joined end to end and cut into rows of exactly seq_len ids; nothing is truncated, the last row is filled with
+        pad_id or, with drop_last, dropped unless full.  Returns numpy uint32[R, seq_len] arrays: rows, then with
+        segments seg (the index of every cell's text in the batch, 0xFFFFFFFF in a pad cell: a block-diagonal
+        attention mask is seg[r, i] == seg[r, j]) and with positions pos (the cell's position in its text's stretch
+        of the row, 0 in a pad cell: position ids); rows alone when neither is asked for.  out=(rows, seg or None,
+        pos or None): contiguous torch tensors of 32-bit integers, [R, seq_len] (R of stream_rows()), on this
+        engine's device: written on the device, no id passes through the host, and the tuple is returned."""
+        s = check_stream(seq_len, pad_id, bos_id, eos_id, drop_last)
+        R, N = self.stream_rows(seq_len, bos_id, eos_id, drop_last)
+        vp = ctypes.c_void_p
+        if out is None:
+            arrs = [np.zeros((R, s.seq_len), dtype=np.uint32) for _ in range(1 + bool(segments) + bool(positions))]
+            ptrs = [a.ctypes.data_as(vp) if a.size else None for a in arrs]
+            seg = ptrs[1] if segments else None
+            pos = ptrs[-1] if positions else None
+            if R:
+                _lib.check(self.L.bpe_gpu_pack_stream(self.ctx, ctypes.byref(s), ptrs[0], seg, pos, 0, R, None, None),
+                           "pack_stream")
+            return tuple(arrs) if len(arrs) > 1 else arrs[0]
+        import torch
+        if not isinstance(out, (tuple, list)) or len(out) != 3 or out[0] is None:
+            raise BpeError("pack_stream: out must be (rows, seg or None, pos or None)")
+        for t in out:
+            if t is None:
+                continue
+            if (not isinstance(t, torch.Tensor) or not t.is_cuda or t.element_size() != 4 or t.is_floating_point()
+                    or tuple(t.shape) != (R, s.seq_len) or not t.is_contiguous()):
+                raise BpeError(f"pack_stream: out must hold contiguous 32-bit integer tensors of shape ({R}, {s.seq_len}) "
+                               "on the GPU")
+            if t.device != out[0].device:
+                raise BpeError("pack_stream: the tensors of out lie on different devices")
+        torch.cuda.current_stream(out[0].device).synchronize()  # (the call writes on the context's stream)
+        ptrs = [vp(t.data_ptr()) if t is not None and t.numel() else None for t in out]
+        if R:
+            _lib.check(self.L.bpe_gpu_pack_stream(self.ctx, ctypes.byref(s), ptrs[0], ptrs[1], ptrs[2], 1, R, None, None),
+                       "pack_stream")
+        return tuple(out)
 
     def load_file(self, path):
         """stream a file into HBM (bpe_gpu_load_fd: pinned double-buffered

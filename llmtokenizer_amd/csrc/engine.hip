@@ -33,6 +33,7 @@
 #include "vocab.hip"
 #include "texts.hip"
 #include "spans.hip"
+#include "stream.hip"
 
 // (bpe_ex.h, src/bpe_texts.c: the host definition of a text batch's offsets and its resident bytes)
 extern "C" int bpe_texts_check(const uint64_t *text_off, size_t T, size_t n, char *msg, size_t msg_cap);
@@ -47,6 +48,8 @@ extern "C" int bpe_vocab_tables(const bpe_gpu_vocab *vocab, uint32_t *fwd, size_
 // (bpe_ex.h, src/bpe_spans.c: the byte length of every token id)
 extern "C" int bpe_span_lens(const uint32_t *pairs, size_t n_merges, const bpe_gpu_specials *specials, const bpe_gpu_vocab *vocab,
                              uint32_t *out, size_t cap, size_t *count, char *msg, size_t msg_cap);
+// (bpe_ex.h, src/bpe_stream.c: the host definition of a packed stream's description)
+extern "C" int bpe_stream_check(const bpe_gpu_stream *s, char *msg, size_t msg_cap);
 
 using namespace bpeamd;
 
@@ -3928,6 +3931,81 @@ int bpe_gpu_pack_spans(bpe_gpu_ctx *c, uint32_t row_len, int side, uint32_t *out
     if (!out_is_device) {
         int r;
         if ((r = d2h_staged(c, out, d_out, cells * 8))) return r;
+    }
+    HIPCHK(hipStreamSynchronize(c->st));
+    return 0;
+}
+
+// ------------------------------------------------ packed streams (stream.hip; the description's check: src/bpe_stream.c)
+
+int bpe_gpu_stream_info(uint64_t *out4) {
+    if (!out4) return BPE_GPU_EINVAL;
+    out4[0] = STR_VEC;
+    out4[1] = (uint64_t)STR_VEC * STR_T;
+    out4[2] = (uint64_t)STR_VEC * STR_T * STR_GRID;
+    out4[3] = STR_WALK;
+    return 0;
+}
+
+int bpe_gpu_pack_stream(bpe_gpu_ctx *c, const bpe_gpu_stream *s, uint32_t *rows, uint32_t *seg, uint32_t *pos,
+                        int out_is_device, size_t rows_cap, size_t *n_rows, uint64_t *n_stream) {
+    if (!c) return BPE_GPU_EINVAL;
+    char msg[400];
+    int r;
+    if ((r = bpe_stream_check(s, msg, sizeof msg))) return fail(r, msg);
+    if (!c->tx_on) return fail(BPE_GPU_ESTATE, "pack_stream: the context holds no text batch (bpe_gpu_load_texts)");
+    if (!c->ids_ready || !c->docs_ready) return fail(BPE_GPU_ESTATE, "pack_stream: no ids: encode_split first");
+    const uint64_t T = c->tx_T, n = c->ids_len, L = s->seq_len;
+    const uint32_t b = (s->flags & BPE_STREAM_BOS) ? 1u : 0u, w = b + ((s->flags & BPE_STREAM_EOS) ? 1u : 0u);
+    const uint64_t N = n + T * w;  // (n and T are below 2^32 each)
+    const uint64_t R = (s->flags & BPE_STREAM_DROP_LAST) ? N / L : (N + L - 1) / L;
+    if (n_rows) *n_rows = (size_t)R;
+    if (n_stream) *n_stream = N;
+    if (!rows) return 0;  // the query
+    if (rows_cap < R) {
+        snprintf(msg, sizeof msg, "pack_stream: rows_cap %zu is below the %llu rows of the stream", rows_cap, (unsigned long long)R);
+        return fail(BPE_GPU_EINVAL, msg);
+    }
+    const uint64_t cells = R * L;
+    uint32_t *d_rows = rows, *d_seg = seg, *d_pos = pos;
+    if (out_is_device) {
+        for (const void *p : {(const void *)rows, (const void *)seg, (const void *)pos}) {
+            if (!p) continue;
+            hipPointerAttribute_t at;
+            if (hipPointerGetAttributes(&at, p) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != c->dev) {
+                (void)hipGetLastError();
+                return fail(BPE_GPU_EINVAL, "pack_stream: rows / seg / pos is no device pointer of the context's device");
+            }
+        }
+        if (((uintptr_t)rows & 3u) || ((uintptr_t)seg & 3u) || ((uintptr_t)pos & 3u))
+            return fail(BPE_GPU_EINVAL, "pack_stream: a pointer that is not 4-byte aligned");
+    }
+    if (!cells) return 0;
+    HIPCHK(hipSetDevice(c->dev));
+    if (!out_is_device) {
+        // (each array begins 16-byte aligned in the buffer whenever the four-cell variant can run: cells * 4 is then a multiple of 16)
+        if ((r = dscratch(c, DS_STR_PACK, cells * 4 * (1 + (seg ? 1 : 0) + (pos ? 1 : 0)), &d_rows))) return r;
+        d_seg = seg ? d_rows + cells : nullptr;
+        d_pos = pos ? d_rows + cells * (seg ? 2 : 1) : nullptr;
+    }
+    const bool vec = L % STR_VEC == 0 && (((uintptr_t)d_rows | (uintptr_t)d_seg | (uintptr_t)d_pos) & 15u) == 0;
+    // a workgroup takes `steps` consecutive tiles: one while the cells fit STR_GRID workgroups, more past that
+    const uint64_t tile = (uint64_t)STR_T * (vec ? STR_VEC : 1), tiles = (cells + tile - 1) / tile;
+    const uint64_t steps = (tiles + STR_GRID - 1) / STR_GRID;
+    const uint32_t grid = (uint32_t)((tiles + steps - 1) / steps);
+    const uint32_t *ids = c->h.ids_out;
+    const uint64_t *toff = (const uint64_t *)c->dscr[DS_TX_IDOFF];
+    if (vec)
+        k_pack_stream<true><<<grid, STR_T, 0, c->st>>>(ids, n, toff, T, N, cells, steps, (uint32_t)L, w, b, s->bos_id, s->eos_id,
+                                                       s->pad_id, d_rows, d_seg, d_pos);
+    else
+        k_pack_stream<false><<<grid, STR_T, 0, c->st>>>(ids, n, toff, T, N, cells, steps, (uint32_t)L, w, b, s->bos_id, s->eos_id,
+                                                        s->pad_id, d_rows, d_seg, d_pos);
+    HIPCHK(hipGetLastError());
+    if (!out_is_device) {
+        if ((r = d2h_staged(c, rows, d_rows, cells * 4))) return r;
+        if (seg && (r = d2h_staged(c, seg, d_seg, cells * 4))) return r;
+        if (pos && (r = d2h_staged(c, pos, d_pos, cells * 4))) return r;
     }
     HIPCHK(hipStreamSynchronize(c->st));
     return 0;

@@ -680,6 +680,7 @@ enum DScr {
     DS_SPN_ERR,          // bpe_gpu_token_spans: error word
     DS_SPN_OUT,          // bpe_gpu_token_spans: the spans [ids][2]; stays with the ids
     DS_SPN_PACK,         // bpe_gpu_pack_spans: the rows of a call with a host pointer
+    DS_STR_PACK,         // bpe_gpu_pack_stream: rows, seg and pos of a call with host pointers
     DS_COUNT
 };
 // bpe_gpu_train_split takes its eight token-sized arrays as one run of slots

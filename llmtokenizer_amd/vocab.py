@@ -217,7 +217,8 @@ class Vocab:
         byte_fallback, dropout, a subword prefix or suffix, an added token with lstrip / rstrip / single_word /
         normalized, any other pre-tokenizer or pattern, a model type other than BPE, and a vocabulary with a
         token its merges do not reach.  A post-processor (Llama 3's adds <|begin_of_text|>) is not applied:
-        the ids are those of `tokenizers` with add_special_tokens=False."""
+        the ids are those of `tokenizers` with add_special_tokens=False (Tokenizer.encode_packed takes a BOS and
+        an EOS by name)."""
         where = str(path)
         with open(path, encoding="utf-8") as f:
             j = json.load(f)
@@ -487,6 +488,52 @@ class Tokenizer:
             return out
         span_rows = torch.empty((n_texts, int(max_length), 2), dtype=torch.int32, device=dev)
         return out + (e.pack_spans(max_length, truncation_side, out=span_rows),)
+
+    def _special_id(self, tok, what):
+        """the id of a BOS / EOS argument: None, an int (a vocabulary id) or the name of one of vocab.specials"""
+        if tok is None or isinstance(tok, (int, np.integer)):
+            return None if tok is None else int(tok)
+        name = tok.encode("utf-8") if isinstance(tok, str) else bytes(tok)
+        specials = [bytes(s) for s in self.vocab.specials]
+        if name not in specials:
+            raise BpeError(f"encode_packed: {what} {tok!r} is none of the vocabulary's specials")
+        return int(self.vocab.special_ids[specials.index(name)])
+
+    def encode_packed(self, texts, seq_len, pad_id, bos=None, eos=None, drop_last=False, return_segments=False,
+                      return_positions=False, return_tensors=None):
+        """Encode a list of texts as encode_batch() does and lay the ids out for training (Engine.pack_stream; the
+        contract: bpe_gpu.h, "Packed streams"): every text wrapped in bos / eos (None: without; an int is taken as
+        a vocabulary id, a str or bytes must be one of vocab.specials and stands for its id), the texts joined end to
+        end and cut into rows of exactly seq_len ids.  Nothing is truncated; the last row is filled with pad_id (any
+        uint32, not checked against the vocabulary) or, with drop_last, dropped unless full.  Returns
+        (rows[, seg][, pos], N): uint32[R, seq_len] arrays, seg (return_segments) the index of every cell's text in
+        the batch, 0xFFFFFFFF in a pad cell, pos (return_positions) the cell's position in its text's stretch of the
+        row, and N the cells of the stream (rows.reshape(-1)[:N] is the stream, the rest pad).
+        return_tensors="pt": torch int32 tensors on the tokenizer's device, filled on the device without fetching the
+        ids to the host (a pad cell's seg reads -1)."""
+        if return_tensors not in (None, "pt"):
+            raise BpeError(f"encode_packed: return_tensors {return_tensors!r} (None or \"pt\")")
+        bos_id, eos_id = self._special_id(bos, "bos"), self._special_id(eos, "eos")
+        api.check_stream(seq_len, pad_id, bos_id, eos_id, drop_last)  # (before any work)
+        if return_tensors == "pt":
+            import torch
+            if not torch.cuda.is_available():  # (see encode_batch)
+                raise BpeError('encode_packed: return_tensors="pt": torch sees no GPU; import torch before the first '
+                               "call into llmtokenizer_amd, so that both share one HIP runtime")
+        e, v = self._eng(), self.vocab
+        e.load_texts(texts)
+        e.split(v.rule, v.specials or None)
+        e.encode_split(v.merges)
+        e.map_ids(v)
+        R, N = e.stream_rows(seq_len, bos_id, eos_id, drop_last)
+        if return_tensors is None:
+            out = e.pack_stream(seq_len, pad_id, bos_id, eos_id, drop_last, return_segments, return_positions)
+            return (out if isinstance(out, tuple) else (out,)) + (N,)
+        dev = torch.device("cuda", self.device)
+        new = lambda: torch.empty((R, int(seq_len)), dtype=torch.int32, device=dev)  # noqa: E731
+        out = e.pack_stream(seq_len, pad_id, bos_id, eos_id, drop_last,
+                            out=(new(), new() if return_segments else None, new() if return_positions else None))
+        return tuple(t for t in out if t is not None) + (N,)
 
     def decode_batch(self, ids, text_off):
         """the inverse of encode_batch(texts): the list of the texts' bytes (NUL bytes dropped, as decode does)"""
