@@ -47,6 +47,10 @@ COBJ_SPANS := $(patsubst $(PKG)/src/%.c,$(BUILD)/%.o,$(CSRC_SPANS))
 # call, so tests/asan_stream needs no model)
 CSRC_STREAM := $(PKG)/src/bpe_stream.c
 COBJ_STREAM := $(patsubst $(PKG)/src/%.c,$(BUILD)/%.o,$(CSRC_STREAM))
+# rows back to texts: src/bpe_rows.c is host code alone (the description's check and the unpack's definition; no
+# engine call, so tests/asan_rows needs no model)
+CSRC_ROWS := $(PKG)/src/bpe_rows.c
+COBJ_ROWS := $(patsubst $(PKG)/src/%.c,$(BUILD)/%.o,$(CSRC_ROWS))
 HIPDEPS := $(wildcard $(PKG)/csrc/*.hip $(PKG)/csrc/*.h) $(PKG)/src/bpe_split_presets.h include/bpe_gpu.h
 
 all: $(PKG)/libbpe_amd.so tools/bpe_main oracle
@@ -60,7 +64,7 @@ $(BUILD)/engine.o: $(HIPDEPS) | $(BUILD)
 $(BUILD)/%.o: $(PKG)/src/%.c $(wildcard include/*.h $(PKG)/src/*.h $(PKG)/csrc/unicode_classes.h) | $(BUILD)
 	$(CC) $(CFLAGS) -c $< -o $@
 
-$(PKG)/libbpe_amd.so: $(BUILD)/engine.o $(COBJ) $(COBJ_GPU) $(COBJ_TS) $(COBJ_SP) $(COBJ_SPECIAL) $(COBJ_VOCAB) $(COBJ_TEXTS) $(COBJ_SPANS) $(COBJ_STREAM)
+$(PKG)/libbpe_amd.so: $(BUILD)/engine.o $(COBJ) $(COBJ_GPU) $(COBJ_TS) $(COBJ_SP) $(COBJ_SPECIAL) $(COBJ_VOCAB) $(COBJ_TEXTS) $(COBJ_SPANS) $(COBJ_STREAM) $(COBJ_ROWS)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -lm -ldl -lpthread
 
 tools/bpe_main: tools/bpe_main.c $(PKG)/libbpe_amd.so
@@ -182,3 +186,12 @@ tests/asan_stream/asan_stream: tests/asan_stream/asan_stream.c $(CSRC_STREAM) $(
 
 asan-stream: tests/asan_stream/asan_stream
 .PHONY: asan-stream
+
+# rows back to texts' host code (src/bpe_rows.c: bpe_rows_check and bpe_unpack_rows_host) the same way, in a
+# stand-alone program that calls no engine function (tests/asan_rows/asan_rows.c); run by tests/test_asan_rows.py
+tests/asan_rows/asan_rows: tests/asan_rows/asan_rows.c $(CSRC_ROWS) $(wildcard include/*.h)
+	$(CC) -O1 -g -std=c11 -D_GNU_SOURCE -fno-omit-frame-pointer -fsanitize=address,undefined \
+	    -fno-sanitize-recover=undefined -Iinclude -o $@ tests/asan_rows/asan_rows.c $(CSRC_ROWS) -lm
+
+asan-rows: tests/asan_rows/asan_rows
+.PHONY: asan-rows

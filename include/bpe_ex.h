@@ -194,6 +194,23 @@ int bpe_pack_stream_host(const uint32_t *ids, size_t n, const uint64_t *text_off
                          uint32_t *rows, uint32_t *seg, uint32_t *pos, size_t rows_cap, size_t *n_rows,
                          uint64_t *n_stream);
 
+/* Rows back to texts (bpe_gpu.h, "Rows back to texts").  bpe_rows_check: 0 for a description bpe_gpu_unpack_rows
+ * takes; BPE_GPU_EINVAL for desc == NULL, a flag bit that is neither BPE_ROWS_PAD nor BPE_ROWS_SKIP, n_stop above 8
+ * and, under BPE_ROWS_SKIP, n_skip above 256 or n_skip ids without a skip pointer; msg (may be NULL) receives a
+ * message that names the field.  No GPU. */
+int bpe_rows_check(const bpe_gpu_rows *desc, char *msg, size_t msg_cap);
+/* The kept ids of rows[B][L] (cells of cell_bytes = 4 or 8, row k at rows + k * row_stride cells; lens: uint32[B] or
+ * NULL), as bpe_gpu.h defines them.  Plain loops, row by row and cell by cell: this is the definition the device is
+ * held to.  *n = the kept ids (may be NULL); text_off (B + 1 entries) and bounds (2 B entries) are written unless
+ * NULL, ids (ids_cap entries of room) too: with ids == NULL the call is the query.  BPE_GPU_EINVAL for what
+ * bpe_rows_check refuses, another cell_bytes, row_stride < L, no rows where there are cells, lens[k] > L (the lowest
+ * such row is in the message; no row is read then) and ids_cap < n; BPE_GPU_ERANGE for L above 2^24; BPE_GPU_EDATA
+ * for a kept 8-byte cell outside 0 .. 2^32 - 1 (the lowest such row is in the message).  After a refusal nothing has
+ * been written but msg (may be NULL).  No GPU. */
+int bpe_unpack_rows_host(const void *rows, int cell_bytes, size_t B, uint32_t L, size_t row_stride, const uint32_t *lens,
+                         const bpe_gpu_rows *desc, uint32_t *ids, size_t ids_cap, size_t *n, uint64_t *text_off,
+                         uint32_t *bounds, char *msg, size_t msg_cap);
+
 /* statistics of the last compress/compress_ex/bpe_train_bytes/bpe_encode_bytes/bpe_encode_docs/bpe_encode_split(_preset) */
 int bpe_last_stats(bpe_gpu_stats *out);
 

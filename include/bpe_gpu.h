@@ -706,6 +706,86 @@ int bpe_gpu_pack_stream(bpe_gpu_ctx *ctx, const bpe_gpu_stream *s, uint32_t *row
    no GPU; for the tests) */
 int bpe_gpu_stream_info(uint64_t *out4);
 
+/* ------------------------------------------------------------------------
+ * Rows back to texts: the ids of a [B, L] grid of cells, as a model hands it
+ * back, cut to the text of every row and decoded; the inverse of
+ * bpe_gpu_pack_texts.  No id passes through the host.
+ *
+ * The contract.  rows[B][L] is a grid of cells of cell_bytes = 4 or 8 bytes; row
+ * k begins row_stride cells after row k - 1 (row_stride >= L, so a column slice
+ * of a contiguous tensor is taken as it lies).  0 <= L <= 2^24; B is any count for
+ * which B * row_stride cells can be addressed.  A 4-byte cell is an id.  An 8-byte
+ * cell is a signed 64-bit value and an id only when it lies in 0 .. 2^32 - 1; no
+ * other value equals a pad, stop or skip id.
+ *
+ * The window of row k is the cells [0, lens[k]) with lens (uint32[B]), else
+ * [0, L).  lens[k] > L is BPE_GPU_EINVAL; the message names the lowest such row.
+ *
+ * The start a_k: with BPE_ROWS_PAD the number of leading window cells equal to
+ * pad_id, else 0.  The end z_k: the first cell c >= a_k of the window whose value
+ * is one of stop[0 .. n_stop) or, with BPE_ROWS_PAD, pad_id; the window's end when
+ * there is none.  The stop cell is not part of the text.  "Leading pads, then the
+ * first stop or pad" reads left-padded rows with pad_id == eos_id as they are
+ * meant; a text whose first token is the pad id loses it (and a text that is
+ * nothing else is empty).
+ *
+ * The kept cells of row k are the cells of [a_k, z_k) in order, without those
+ * whose id is in skip[0 .. n_skip) under BPE_ROWS_SKIP.  A kept 8-byte cell outside
+ * 0 .. 2^32 - 1 is BPE_GPU_EDATA; the message names the lowest such row.  A cell
+ * outside [a_k, z_k) is never judged, whatever it holds (an ignore index of -100,
+ * garbage behind the EOS), nor is a skipped one.
+ *
+ * The results: ids uint32[n], the kept cells of all rows joined; text_off
+ * uint64[B + 1], row k's ids being ids[text_off[k] .. text_off[k + 1]); bounds
+ * uint32[B][2] = (a_k, z_k), so z_k - a_k is the length of what row k generated.
+ * bpe_gpu_unpack_rows computes them on the device (rows.hip) and keeps them in
+ * scratch slots of their own: they disturb no resident ids of an encode and no
+ * encode, load or decode disturbs them; bpe_gpu_trim drops them.
+ * bpe_gpu_decode_rows decodes them as bpe_gpu_decode_docs_vocab / _special /
+ * bpe_gpu_decode_docs would decode ids and text_off fetched and handed back (NUL
+ * bytes dropped; an id the list or the vocabulary does not hold is BPE_GPU_EDATA
+ * "unknown token id", which only a kept cell can raise).  bpe_ex.h
+ * bpe_unpack_rows_host is the same in plain loops.
+ * ---------------------------------------------------------------------- */
+#define BPE_ROWS_PAD 1u   /* flags: pad_id counts */
+#define BPE_ROWS_SKIP 2u  /* ... the skip list counts */
+#define BPE_ROWS_FLAGS 3u
+#define BPE_ROWS_LEN_MAX (1u << 24)
+#define BPE_ROWS_STOP_MAX 8
+#define BPE_ROWS_SKIP_MAX 256
+typedef struct {
+    uint32_t flags, pad_id;
+    uint32_t n_stop, stop[BPE_ROWS_STOP_MAX];
+    uint32_t n_skip;
+    const uint32_t *skip; /* n_skip ids in any order, duplicates allowed (the library sorts a copy); read under BPE_ROWS_SKIP */
+} bpe_gpu_rows;
+/* Unpack rows[B][L] (cells of cell_bytes, row_stride cells from row to row) as `desc` says and keep ids, text_off
+   and bounds on the device; *n = the ids.  rows_is_device != 0: a device pointer on the context's device (a tensor's
+   data pointer), aligned to its cell size, read on the context's stream; else host memory, uploaded row by row
+   (a 2-D copy that honours row_stride).  lens (may be NULL) and lens_is_device the same for the windows.
+   BPE_GPU_EINVAL for what bpe_rows_check (bpe_ex.h) refuses, another cell_bytes, row_stride < L, a device pointer
+   that is none of the context's device or not aligned, and lens[k] > L; BPE_GPU_ERANGE for L above 2^24;
+   BPE_GPU_EDATA for a kept 8-byte cell that is no id.  After a refusal nothing is kept (bpe_gpu_fetch_rows and
+   bpe_gpu_decode_rows return BPE_GPU_ESTATE) and the context goes on working. */
+int bpe_gpu_unpack_rows(bpe_gpu_ctx *ctx, const void *rows, int rows_is_device, int cell_bytes, size_t B, uint32_t L,
+                        size_t row_stride, const uint32_t *lens, int lens_is_device, const bpe_gpu_rows *desc, size_t *n);
+/* The last unpack's results.  Two-phase: *n = the ids and *B = the rows are always reported (each may be NULL);
+   ids (ids_cap entries of room), text_off (B_cap + 1) and bounds (2 * B_cap) are each written unless NULL.
+   BPE_GPU_EINVAL for ids_cap < n with ids, B_cap < B with text_off or bounds; BPE_GPU_ESTATE without an unpack. */
+int bpe_gpu_fetch_rows(bpe_gpu_ctx *ctx, uint32_t *ids, size_t ids_cap, size_t *n, uint64_t *text_off, uint32_t *bounds,
+                       size_t B_cap, size_t *B);
+/* Decode the last unpack's ids, row by row: out[byte_off[k] .. byte_off[k + 1]) is row k's text (byte_off: B + 1
+   entries, may be NULL).  specials and vocab may each be NULL: with a vocabulary the ids are its ids, checked as
+   bpe_gpu_decode_docs_vocab checks them; without, internal ids.  Two-phase as the decoders: out == NULL reports
+   *out_len alone.  The unpacked ids stay as they are and can be fetched or decoded again.  BPE_GPU_ESTATE when
+   nothing has been unpacked. */
+int bpe_gpu_decode_rows(bpe_gpu_ctx *ctx, const uint32_t *pairs, size_t n_merges, const bpe_gpu_specials *specials,
+                        const bpe_gpu_vocab *vocab, uint8_t *out, size_t cap, size_t *out_len, uint64_t *byte_off);
+/* out4 = {cells one lane of the vector variants (k_rows_bounds / k_rows_gather <., true>) takes per step, cells a wave
+   takes per step then (a wave owns a row; the one-cell variants take a quarter), rows per workgroup, rows the largest
+   grid takes in one step (more rows: a wave goes on to further rows)} (pure function, no GPU; for the tests) */
+int bpe_gpu_rows_info(uint64_t *out4);
+
 int bpe_gpu_get_stats(bpe_gpu_ctx *ctx, bpe_gpu_stats *st);
 
 /* Position-keyed checksum of the ids of the last train / encode, computed in

@@ -61,6 +61,9 @@ EXPORTS = [
     "bpe_token_spans_host",
     # bpe_gpu.h / bpe_ex.h: packed streams
     "bpe_gpu_pack_stream", "bpe_gpu_stream_info", "bpe_stream_check", "bpe_pack_stream_host",
+    # bpe_gpu.h / bpe_ex.h: rows back to texts
+    "bpe_gpu_unpack_rows", "bpe_gpu_fetch_rows", "bpe_gpu_decode_rows", "bpe_gpu_rows_info", "bpe_rows_check",
+    "bpe_unpack_rows_host",
 ]
 
 
@@ -78,6 +81,12 @@ class VocabIds(ctypes.Structure):
 class Stream(ctypes.Structure):
     """bpe_gpu.h bpe_gpu_stream"""
     _fields_ = [(n, ctypes.c_uint32) for n in ("seq_len", "flags", "bos_id", "eos_id", "pad_id")]
+
+
+class Rows(ctypes.Structure):
+    """bpe_gpu.h bpe_gpu_rows"""
+    _fields_ = [("flags", ctypes.c_uint32), ("pad_id", ctypes.c_uint32), ("n_stop", ctypes.c_uint32),
+                ("stop", ctypes.c_uint32 * 8), ("n_skip", ctypes.c_uint32), ("skip", ctypes.c_void_p)]
 
 
 class GpuStats(ctypes.Structure):
@@ -294,6 +303,15 @@ def load():
     L.bpe_gpu_stream_info.argtypes = [vp]
     L.bpe_stream_check.argtypes = [stp, ctypes.c_char_p, sz]
     L.bpe_pack_stream_host.argtypes = [vp, sz, vp, sz, stp, vp, vp, vp, sz, ctypes.POINTER(sz), u64p]
+    rwp = ctypes.POINTER(Rows)
+    L.bpe_gpu_unpack_rows.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, sz, ctypes.c_uint32, sz, vp, ctypes.c_int, rwp,
+                                      ctypes.POINTER(sz)]
+    L.bpe_gpu_fetch_rows.argtypes = [vp, vp, sz, ctypes.POINTER(sz), vp, vp, sz, ctypes.POINTER(sz)]
+    L.bpe_gpu_decode_rows.argtypes = [vp, vp, sz, spp, vop, vp, sz, ctypes.POINTER(sz), vp]
+    L.bpe_gpu_rows_info.argtypes = [vp]
+    L.bpe_rows_check.argtypes = [rwp, ctypes.c_char_p, sz]
+    L.bpe_unpack_rows_host.argtypes = [vp, ctypes.c_int, sz, ctypes.c_uint32, sz, vp, rwp, vp, sz, ctypes.POINTER(sz), vp, vp,
+                                       ctypes.c_char_p, sz]
     L.bpe_release_engines.argtypes = []
     L.bpe_release_engines.restype = None
     _LIB = L

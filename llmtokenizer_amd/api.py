@@ -634,6 +634,105 @@ def stream_info():
     return {"per_thread": int(out[0]), "per_block": int(out[1]), "per_grid": int(out[2]), "walk": int(out[3])}
 
 
+ROWS_PAD, ROWS_SKIP = 1, 2  # bpe_gpu.h BPE_ROWS_*
+
+
+class _Rows:
+    """a bpe_gpu.h bpe_gpu_rows and the skip array it points into"""
+
+    def __init__(self, desc, skip):
+        self.desc, self.skip, self.ref = desc, skip, ctypes.byref(desc)
+
+
+def check_rows(pad_id=None, stop_ids=(), skip_ids=(), flags=None):
+    """The description of an unpack (bpe_gpu.h bpe_gpu_rows) that unpack_rows_host and Engine.unpack_rows take,
+    checked by bpe_ex.h bpe_rows_check: pad_id (None: rows are not padded), at most 8 stop_ids, at most 256 skip_ids
+    (none, or None: nothing is skipped), every id a uint32.  flags (for the tests): the flag word as it is, in place of the one
+    the arguments make.  Raises BpeError with the code's text and a message that names the field.  No GPU."""
+    L = _lib.load()
+    stops = [int(s) for s in stop_ids]
+    skips = [] if skip_ids is None else [int(s) for s in np.asarray(skip_ids).reshape(-1).tolist()]
+    pad = 0 if pad_id is None else int(pad_id)
+    f = (ROWS_PAD if pad_id is not None else 0) | (ROWS_SKIP if skips else 0) if flags is None else int(flags)
+    if any(not 0 <= v <= 0xFFFFFFFF for v in stops + skips + [pad, f]):
+        raise BpeError("rows: pad_id, stop_ids, skip_ids and flags are uint32")
+    skip = np.array(skips, dtype=np.uint32)
+    d = _lib.Rows(f, pad, len(stops), (ctypes.c_uint32 * 8)(*stops[:8]), skip.size,
+                  skip.ctypes.data_as(ctypes.c_void_p) if skip.size else None)
+    msg = ctypes.create_string_buffer(400)
+    rc = L.bpe_rows_check(ctypes.byref(d), msg, len(msg))
+    if rc:
+        raise BpeError(f"check_rows: {L.bpe_gpu_strerror(rc).decode()} ({msg.value.decode(errors='replace')})")
+    return _Rows(d, skip)
+
+
+ROWS_WHAT = ("a 2-D numpy array of uint32, int32, int64 or uint64 whose rows are contiguous, or a 2-D torch tensor of "
+             "int32 or int64 on the engine's device with stride(1) == 1 and stride(0) >= shape[1]")
+
+
+def _rows_numpy(rows, what):
+    """(array, cell_bytes, B, L, row_stride in cells) of a numpy rows argument, without a copy where its rows are
+    contiguous"""
+    if rows.ndim != 2 or rows.dtype not in (np.uint32, np.int32, np.int64, np.uint64):
+        raise BpeError(f"{what}: rows of shape {rows.shape} and dtype {rows.dtype}: pass {ROWS_WHAT}")
+    B, L = rows.shape
+    cb = rows.dtype.itemsize
+    ok = (L <= 1 or rows.strides[1] == cb) and (B <= 1 or (rows.strides[0] % cb == 0 and rows.strides[0] >= L * cb
+                                                           and rows.strides[0] > 0))
+    if not ok or not rows.dtype.isnative:
+        rows = np.ascontiguousarray(rows)
+    stride = rows.strides[0] // cb if B > 1 else L
+    return rows, cb, B, L, max(stride, L)
+
+
+def _lens_numpy(lens, B, what):
+    lens = np.ascontiguousarray(lens)
+    if lens.shape != (B,) or lens.dtype.kind not in "iu" or (lens.size and (lens.min() < 0 or lens.max() > 0xFFFFFFFF)):
+        raise BpeError(f"{what}: lens must hold one uint32 per row ({B})")
+    return lens.astype(np.uint32)
+
+
+def unpack_rows_host(rows, lens=None, pad_id=None, stop_ids=(), skip_ids=()):
+    """The texts' ids of a grid of cells, on the host in plain loops (bpe_ex.h bpe_unpack_rows_host: the definition
+    Engine.unpack_rows is held to; the contract: bpe_gpu.h, "Rows back to texts").  rows: a 2-D numpy array of uint32,
+    int32, int64 or uint64; a 64-bit cell is an id only in 0 .. 2^32 - 1.  Row k's window is its first lens[k] cells
+    (lens None: all); its text begins behind the leading cells equal to pad_id (None: at 0) and ends before the first
+    cell that is one of stop_ids or pad_id, or at the window's end; ids in skip_ids are left out.  Returns (ids
+    uint32[n], text_off uint64[B + 1], bounds uint32[B, 2]): row k's ids are ids[text_off[k]:text_off[k + 1]] and
+    bounds[k] = (start, end).  No GPU."""
+    L_ = _lib.load()
+    d = check_rows(pad_id, stop_ids, skip_ids)
+    rows, cb, B, L, stride = _rows_numpy(np.asarray(rows), "unpack_rows_host")
+    vp = ctypes.c_void_p
+    if lens is not None:
+        lens = _lens_numpy(lens, B, "unpack_rows_host")
+    n = ctypes.c_size_t(0)
+    msg = ctypes.create_string_buffer(400)
+    args = (rows.ctypes.data_as(vp) if rows.size else None, cb, B, L, stride,
+            lens.ctypes.data_as(vp) if lens is not None and B else None, d.ref)
+
+    rc = L_.bpe_unpack_rows_host(*args, None, 0, ctypes.byref(n), None, None, msg, len(msg))
+    if rc:
+        raise BpeError(f"unpack_rows_host: {L_.bpe_gpu_strerror(rc).decode()} ({msg.value.decode(errors='replace')})")
+    ids = np.zeros(n.value, dtype=np.uint32)
+    text_off = np.zeros(B + 1, dtype=np.uint64)
+    bounds = np.zeros((B, 2), dtype=np.uint32)
+    rc = L_.bpe_unpack_rows_host(*args, ids.ctypes.data_as(vp), ids.size, ctypes.byref(n), text_off.ctypes.data_as(vp),
+                                 bounds.ctypes.data_as(vp), msg, len(msg))
+    if rc:
+        raise BpeError(f"unpack_rows_host: {L_.bpe_gpu_strerror(rc).decode()} ({msg.value.decode(errors='replace')})")
+    return ids, text_off, bounds
+
+
+def rows_info():
+    """{cells one lane of the vector unpacking kernels takes per step, cells a wave (which owns a row) takes per step
+    then, rows per workgroup, rows the largest grid takes in one step} (bpe_gpu_rows_info; the one-cell variants take a
+    quarter of the first two; no GPU; for the tests)"""
+    out = np.zeros(4, dtype=np.uint64)
+    _lib.check(_lib.load().bpe_gpu_rows_info(out.ctypes.data_as(ctypes.c_void_p)), "rows_info")
+    return {"per_lane": int(out[0]), "per_wave": int(out[1]), "rows_per_block": int(out[2]), "rows_per_grid": int(out[3])}
+
+
 PACK_SIDES = {"right": 0, "left": 1}  # the side a longer text is cut at: "right" keeps its first ids, "left" its last
 
 
@@ -814,6 +913,89 @@ class Engine:
             _lib.check(self.L.bpe_gpu_pack_stream(self.ctx, ctypes.byref(s), ptrs[0], ptrs[1], ptrs[2], 1, R, None, None),
                        "pack_stream")
         return tuple(out)
+
+    def unpack_rows(self, rows, lens=None, pad_id=None, stop_ids=(), skip_ids=()):
+        """the texts' ids of a grid of cells, cut on the device (bpe_gpu_unpack_rows; the contract: bpe_gpu.h, "Rows
+        back to texts"; the arguments: unpack_rows_host).  rows: a numpy array as unpack_rows_host takes it, or a 2-D
+        torch tensor of int32 or int64 on this engine's device with stride(1) == 1 and stride(0) >= shape[1] (so
+        out[:, P:] of a contiguous tensor is read where it lies, without a copy): no id passes through the host.
+        lens: a numpy array or a torch int32 tensor on the same device.  The ids, their offsets and the bounds stay on
+        the device for decode_rows() and are returned as numpy arrays (ids uint32[n], text_off uint64[B + 1], bounds
+        uint32[B, 2]).  They live apart from the resident ids of an encode: neither disturbs the other."""
+        self._unpack_rows(rows, lens, pad_id, stop_ids, skip_ids)
+        return self.fetch_rows()
+
+    def _unpack_rows(self, rows, lens, pad_id, stop_ids, skip_ids):
+        d = check_rows(pad_id, stop_ids, skip_ids)
+        vp = ctypes.c_void_p
+        n = ctypes.c_size_t(0)
+        if isinstance(rows, np.ndarray) or not hasattr(rows, "data_ptr"):
+            rows, cb, B, L, stride = _rows_numpy(np.asarray(rows), "unpack_rows")
+            rp, on_dev = (rows.ctypes.data_as(vp) if rows.size else None), 0
+            dev = None
+        else:
+            import torch
+            if (not isinstance(rows, torch.Tensor) or rows.dim() != 2 or rows.dtype not in (torch.int32, torch.int64)
+                    or not rows.is_cuda or (rows.shape[1] > 1 and rows.stride(1) != 1)
+                    or (rows.shape[0] > 1 and rows.stride(0) < rows.shape[1])):
+                where = f" on {rows.device}" if isinstance(rows, torch.Tensor) else ""
+                raise BpeError(f"unpack_rows: rows of shape {tuple(rows.shape)}, dtype {rows.dtype} and strides "
+                               f"{tuple(rows.stride())}{where}: pass {ROWS_WHAT}")
+            (B, L), cb, dev = rows.shape, rows.element_size(), rows.device
+            stride = max(rows.stride(0), L) if B > 1 else L
+            rp, on_dev = (vp(rows.data_ptr()) if rows.numel() else None), 1
+            torch.cuda.current_stream(dev).synchronize()  # (the call reads on the context's stream)
+        lp, lens_dev = None, 0
+        if lens is not None and hasattr(lens, "data_ptr"):
+            import torch
+            if (not isinstance(lens, torch.Tensor) or lens.dtype != torch.int32 or tuple(lens.shape) != (B,)
+                    or not lens.is_contiguous() or not lens.is_cuda or (dev is not None and lens.device != dev)):
+                raise BpeError(f"unpack_rows: lens must be a numpy array or a contiguous torch int32 tensor of shape ({B},) "
+                               "on the device of rows")
+            if dev is None:
+                torch.cuda.current_stream(lens.device).synchronize()
+            lp, lens_dev = (vp(lens.data_ptr()) if B else None), 1
+        elif lens is not None:
+            lens = _lens_numpy(lens, B, "unpack_rows")
+            lp = lens.ctypes.data_as(vp) if B else None
+        _lib.check(self.L.bpe_gpu_unpack_rows(self.ctx, rp, on_dev, cb, B, L, stride, lp, lens_dev, d.ref, ctypes.byref(n)),
+                   "unpack_rows")
+        return B, n.value
+
+    def fetch_rows(self):
+        """(ids, text_off, bounds) of the last unpack_rows(), as it returned them (bpe_gpu_fetch_rows)"""
+        n, B = ctypes.c_size_t(0), ctypes.c_size_t(0)
+        _lib.check(self.L.bpe_gpu_fetch_rows(self.ctx, None, 0, ctypes.byref(n), None, None, 0, ctypes.byref(B)), "fetch_rows")
+        ids = np.zeros(n.value, dtype=np.uint32)
+        text_off = np.zeros(B.value + 1, dtype=np.uint64)
+        bounds = np.zeros((B.value, 2), dtype=np.uint32)
+        vp = ctypes.c_void_p
+        _lib.check(self.L.bpe_gpu_fetch_rows(self.ctx, ids.ctypes.data_as(vp) if n.value else None, n.value, ctypes.byref(n),
+                                             text_off.ctypes.data_as(vp), bounds.ctypes.data_as(vp) if B.value else None,
+                                             B.value, ctypes.byref(B)), "fetch_rows")
+        return ids, text_off, bounds
+
+    def decode_rows(self, merges, specials=None, vocab=None):
+        """(bytes, byte offsets) of the last unpack_rows(), row k's text being bytes[off[k]:off[k + 1]]
+        (bpe_gpu_decode_rows): what decode_docs(ids, text_off, merges, specials, vocab) of the unpacked ids gives,
+        without the ids leaving the device.  The unpacked ids stay and can be decoded again."""
+        m = np.ascontiguousarray(merges, dtype=np.uint32).reshape(-1)
+        vp = ctypes.c_void_p
+        sp = cv = None
+        if specials is not None:
+            check_specials(specials)
+            sp = _Specials(specials)
+        if vocab is not None:
+            cv = vocab.c_vocab()
+        B, n = ctypes.c_size_t(0), ctypes.c_size_t(0)
+        args = (self.ctx, m.ctypes.data_as(vp), m.size // 2, sp.ref if sp else None, cv.ref if cv else None)
+        _lib.check(self.L.bpe_gpu_decode_rows(*args, None, 0, ctypes.byref(n), None), "decode_rows")
+        _lib.check(self.L.bpe_gpu_fetch_rows(self.ctx, None, 0, None, None, None, 0, ctypes.byref(B)), "fetch_rows")
+        out = np.zeros(max(n.value, 1), dtype=np.uint8)
+        bo = np.zeros(B.value + 1, dtype=np.uint64)
+        _lib.check(self.L.bpe_gpu_decode_rows(*args, out.ctypes.data_as(vp), out.size, ctypes.byref(n), bo.ctypes.data_as(vp)),
+                   "decode_rows")
+        return out[: n.value].tobytes(), bo
 
     def load_file(self, path):
         """stream a file into HBM (bpe_gpu_load_fd: pinned double-buffered

@@ -34,6 +34,7 @@
 #include "texts.hip"
 #include "spans.hip"
 #include "stream.hip"
+#include "rows.hip"
 
 // (bpe_ex.h, src/bpe_texts.c: the host definition of a text batch's offsets and its resident bytes)
 extern "C" int bpe_texts_check(const uint64_t *text_off, size_t T, size_t n, char *msg, size_t msg_cap);
@@ -50,6 +51,7 @@ extern "C" int bpe_span_lens(const uint32_t *pairs, size_t n_merges, const bpe_g
                              uint32_t *out, size_t cap, size_t *count, char *msg, size_t msg_cap);
 // (bpe_ex.h, src/bpe_stream.c: the host definition of a packed stream's description)
 extern "C" int bpe_stream_check(const bpe_gpu_stream *s, char *msg, size_t msg_cap);
+extern "C" int bpe_rows_check(const bpe_gpu_rows *desc, char *msg, size_t msg_cap);
 
 using namespace bpeamd;
 
@@ -343,6 +345,10 @@ struct bpe_gpu_ctx {
     // split_ready, split_n counts the break pieces too and DS_TX_PIECE / DS_TX_SPLIT hold what split_run left.
     bool tx_on = false;
     uint64_t tx_T = 0;
+    // the last bpe_gpu_unpack_rows: scratch slots DS_ROWS_IDS, DS_ROWS_OFF and DS_ROWS_BOUNDS hold rows_n ids of rows_B
+    // rows.  Nothing but the next unpack and bpe_gpu_trim (which frees the slots) touches them.
+    bool rows_ready = false;
+    uint64_t rows_B = 0, rows_n = 0;
     // the last bpe_gpu_train_split over those offsets: its merges (host), bpe_gpu_train_split_info's fields and
     // the piece table (scratch slots DS_TS_ESTART, DS_TS_ELEN, DS_TS_ECNT).  Valid while split_ready: whatever drops
     // the offsets drops these.
@@ -3077,9 +3083,12 @@ static uint32_t vm_grid(uint64_t len) {
 // bpe_gpu_decode_docs_special: the ids V0 .. V0 + S - 1 past the merge list's are the (checked) specials, whose
 // lengths follow the merge list's in elen and whose bytes k_sp_dec_expand copies.  With a vocabulary (checked by
 // the caller) the uploaded ids are its ids and are turned into internal ones first (k_ids_unmap).
-static int decode_run(bpe_gpu_ctx *c, const uint32_t *ids, size_t len, const uint32_t *pairs, size_t n_merges,
-                      const bpe_gpu_specials *sp, uint8_t *out, size_t cap, size_t *out_len,
-                      const bpe_gpu_vocab *vocab = nullptr) {
+// decode_core is the whole of it but for where the ids come from: `ids_from` says whether `ids` is host memory
+// (decode_run: the upload) or lies on the device already (bpe_gpu_decode_rows); either way they are copied into
+// scratch slot DS_DEC_IDS at the same place in the stream's order, since k_ids_unmap rewrites them in place.
+static int decode_core(bpe_gpu_ctx *c, const uint32_t *ids, hipMemcpyKind ids_from, size_t len, const uint32_t *pairs,
+                       size_t n_merges, const bpe_gpu_specials *sp, uint8_t *out, size_t cap, size_t *out_len,
+                       const bpe_gpu_vocab *vocab) {
     if (!c || !out_len || (!ids && len) || (!pairs && n_merges)) return BPE_GPU_EINVAL;
     if (n_merges > 0xFFFFFEFFull) return fail(BPE_GPU_ERANGE, "merge list too long");
     const uint32_t S = sp ? (uint32_t)sp->count : 0u;
@@ -3110,7 +3119,7 @@ static int decode_run(bpe_gpu_ctx *c, const uint32_t *ids, size_t len, const uin
         HIPCHK(hipMemcpyAsync(d_soff, sp_off.data(), (S + 1) * 4, hipMemcpyHostToDevice, c->st));
     }
     HIPCHK(hipMemsetAsync(d_err, 0, 8, c->st));
-    if (len) HIPCHK(hipMemcpyAsync(d_ids, ids, len * 4, hipMemcpyHostToDevice, c->st));
+    if (len) HIPCHK(hipMemcpyAsync(d_ids, ids, len * 4, ids_from, c->st));
     if (n_merges) HIPCHK(hipMemcpyAsync(d_pairs, pairs, n_merges * 8, hipMemcpyHostToDevice, c->st));
     std::vector<uint32_t> inv;  // (lives until the synchronisation below)
     if (vocab && len) {
@@ -3163,6 +3172,12 @@ static int decode_run(bpe_gpu_ctx *c, const uint32_t *ids, size_t len, const uin
     HIPCHK(hipMemcpyAsync(out, d_out, total, hipMemcpyDeviceToHost, c->st));
     HIPCHK(hipStreamSynchronize(c->st));
     return 0;
+}
+
+static int decode_run(bpe_gpu_ctx *c, const uint32_t *ids, size_t len, const uint32_t *pairs, size_t n_merges,
+                      const bpe_gpu_specials *sp, uint8_t *out, size_t cap, size_t *out_len,
+                      const bpe_gpu_vocab *vocab = nullptr) {
+    return decode_core(c, ids, hipMemcpyHostToDevice, len, pairs, n_merges, sp, out, cap, out_len, vocab);
 }
 
 int bpe_gpu_decode(bpe_gpu_ctx *c, const uint32_t *ids, size_t len, const uint32_t *pairs, size_t n_merges,
@@ -3389,6 +3404,7 @@ int bpe_gpu_trim(bpe_gpu_ctx *c) {
     c->sp_M = 0;
     c->tx_on = false;
     c->tx_T = 0;
+    c->rows_ready = false;
     for (int k = 0; k < DS_COUNT; k++) {
         if (c->dscr[k]) (void)hipFree(c->dscr[k]);
         c->dscr[k] = nullptr;
@@ -4007,6 +4023,193 @@ int bpe_gpu_pack_stream(bpe_gpu_ctx *c, const bpe_gpu_stream *s, uint32_t *rows,
         if (seg && (r = d2h_staged(c, seg, d_seg, cells * 4))) return r;
         if (pos && (r = d2h_staged(c, pos, d_pos, cells * 4))) return r;
     }
+    HIPCHK(hipStreamSynchronize(c->st));
+    return 0;
+}
+
+// ------------------------------------------------ rows back to texts (rows.hip; the description's check: src/bpe_rows.c)
+
+int bpe_gpu_rows_info(uint64_t *out4) {
+    if (!out4) return BPE_GPU_EINVAL;
+    out4[0] = ROWS_VEC;
+    out4[1] = (uint64_t)ROWS_VEC * 64;
+    out4[2] = ROWS_PER_WG;
+    out4[3] = (uint64_t)ROWS_PER_WG * ROWS_GRID;
+    return 0;
+}
+
+}  // extern "C"
+
+// `what` (rows / lens) must be a device pointer of the context's device, aligned to `align` bytes
+static int rows_device_ptr(bpe_gpu_ctx *c, const void *p, size_t align, const char *what) {
+    char msg[200];
+    if ((uintptr_t)p & (align - 1)) {
+        snprintf(msg, sizeof msg, "unpack_rows: %s is a device pointer that is not %zu-byte aligned", what, align);
+        return fail(BPE_GPU_EINVAL, msg);
+    }
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, p) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != c->dev) {
+        (void)hipGetLastError();
+        snprintf(msg, sizeof msg, "unpack_rows: %s is no device pointer of the context's device", what);
+        return fail(BPE_GPU_EINVAL, msg);
+    }
+    return 0;
+}
+
+template <typename CELL>
+static void rows_launch(bpe_gpu_ctx *c, bool gather, bool vec, uint32_t grid, const void *rows, uint64_t B, uint32_t L,
+                        uint64_t stride, const uint32_t *lens, const RowsDesc &d, const uint32_t *skip, uint32_t *bounds,
+                        uint64_t *cnt, unsigned long long *err, const uint64_t *off, uint32_t *ids) {
+    const CELL *r = (const CELL *)rows;
+    if (!gather) {
+        if (vec) k_rows_bounds<CELL, true><<<grid, ROWS_T, 0, c->st>>>(r, B, L, stride, lens, d, skip, bounds, cnt, err);
+        else k_rows_bounds<CELL, false><<<grid, ROWS_T, 0, c->st>>>(r, B, L, stride, lens, d, skip, bounds, cnt, err);
+    } else {
+        if (vec) k_rows_gather<CELL, true><<<grid, ROWS_T, 0, c->st>>>(r, B, L, stride, d, skip, bounds, off, ids);
+        else k_rows_gather<CELL, false><<<grid, ROWS_T, 0, c->st>>>(r, B, L, stride, d, skip, bounds, off, ids);
+    }
+}
+
+extern "C" {
+
+int bpe_gpu_unpack_rows(bpe_gpu_ctx *c, const void *rows, int rows_is_device, int cell_bytes, size_t B, uint32_t L,
+                        size_t row_stride, const uint32_t *lens, int lens_is_device, const bpe_gpu_rows *desc, size_t *n) {
+    if (!c) return BPE_GPU_EINVAL;
+    char msg[400];
+    int r;
+    if ((r = bpe_rows_check(desc, msg, sizeof msg))) return fail(r, msg);
+    if (cell_bytes != 4 && cell_bytes != 8) return fail(BPE_GPU_EINVAL, "unpack_rows: cell_bytes is neither 4 nor 8");
+    if (L > BPE_ROWS_LEN_MAX) return fail(BPE_GPU_ERANGE, "unpack_rows: L above 2^24");
+    if (row_stride < L) {
+        snprintf(msg, sizeof msg, "unpack_rows: row_stride %zu below L %u", row_stride, (unsigned)L);
+        return fail(BPE_GPU_EINVAL, msg);
+    }
+    const size_t cs = (size_t)cell_bytes;
+    if (B && row_stride && B > (SIZE_MAX / cs) / row_stride) return fail(BPE_GPU_ERANGE, "unpack_rows: B * row_stride cells cannot be addressed");
+    if (!rows && B && L) return fail(BPE_GPU_EINVAL, "unpack_rows: rows is NULL");
+    if (rows && rows_is_device && (r = rows_device_ptr(c, rows, cs, "rows"))) return r;
+    if (lens && lens_is_device && (r = rows_device_ptr(c, lens, 4, "lens"))) return r;
+    HIPCHK(hipSetDevice(c->dev));
+    c->rows_ready = false;  // (what the last unpack left is overwritten from here on)
+
+    // the rows, the windows and the skip list on the device
+    const void *d_rows = rows;
+    uint64_t stride = row_stride;
+    if (!rows_is_device && B && L) {
+        void *p;
+        if ((r = dscratch(c, DS_ROWS_IN, B * L * cs, &p))) return r;
+        HIPCHK(hipMemcpy2DAsync(p, L * cs, rows, row_stride * cs, L * cs, B, hipMemcpyHostToDevice, c->st));
+        d_rows = p;
+        stride = L;
+    }
+    const uint32_t *d_lens = lens;
+    if (lens && !lens_is_device && B) {
+        uint32_t *p;
+        if ((r = dscratch(c, DS_ROWS_LENS, B * 4, &p))) return r;
+        HIPCHK(hipMemcpyAsync(p, lens, B * 4, hipMemcpyHostToDevice, c->st));
+        d_lens = p;
+    }
+    RowsDesc d = {};
+    d.pad_on = (desc->flags & BPE_ROWS_PAD) ? 1u : 0u;
+    d.pad = desc->pad_id;
+    d.n_stop = desc->n_stop;
+    for (uint32_t j = 0; j < desc->n_stop; j++) d.stop[j] = desc->stop[j];
+    std::vector<uint32_t> skip;  // (lives until the synchronisation below)
+    uint32_t *d_skip = nullptr;
+    if ((desc->flags & BPE_ROWS_SKIP) && desc->n_skip) {
+        skip.assign(desc->skip, desc->skip + desc->n_skip);
+        std::sort(skip.begin(), skip.end());
+        while (skip.size() & (skip.size() - 1)) skip.push_back(skip.back());  // up to a power of two: the search's halvings
+        for (size_t p = skip.size(); p; p >>= 1) d.skip_steps++;
+        if ((r = dscratch(c, DS_ROWS_SKIP, skip.size() * 4, &d_skip))) return r;
+        HIPCHK(hipMemcpyAsync(d_skip, skip.data(), skip.size() * 4, hipMemcpyHostToDevice, c->st));
+    }
+    uint32_t *d_bounds, *d_ids;
+    uint64_t *d_cnt, *d_off;
+    unsigned long long *d_err;
+    if ((r = dscratch(c, DS_ROWS_BOUNDS, std::max<size_t>(B, 1) * 8, &d_bounds)) || (r = dscratch(c, DS_ROWS_CNT, (B + 1) * 8, &d_cnt)) ||
+        (r = dscratch(c, DS_ROWS_OFF, (B + 1) * 8, &d_off)) || (r = dscratch(c, DS_ROWS_ERR, 64, &d_err)))
+        return r;
+    HIPCHK(hipMemsetAsync(d_err, 0xFF, 16, c->st));  // (ROWS_NO_ROW twice)
+    HIPCHK(hipMemsetAsync(d_cnt + B, 0, 8, c->st));
+    // four cells per lane: a lane's vector must lie in one row and be aligned
+    const bool vec = L % ROWS_VEC == 0 && ((uintptr_t)d_rows & 15u) == 0 && (stride * cs) % 16 == 0;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>((B + ROWS_PER_WG - 1) / ROWS_PER_WG, ROWS_GRID);
+    if (B) {
+        if (cell_bytes == 4) rows_launch<uint32_t>(c, false, vec, grid, d_rows, B, L, stride, d_lens, d, d_skip, d_bounds, d_cnt, d_err, nullptr, nullptr);
+        else rows_launch<int64_t>(c, false, vec, grid, d_rows, B, L, stride, d_lens, d, d_skip, d_bounds, d_cnt, d_err, nullptr, nullptr);
+        HIPCHK(hipGetLastError());
+    }
+    r = ROCPRIM_RUN(c, DS_ROWS_TMP, rocprim::exclusive_scan(tmp, tb, d_cnt, d_off, (uint64_t)0, B + 1, rocprim::plus<uint64_t>(), c->st));
+    if (r) return r;
+    unsigned long long err[2] = {ROWS_NO_ROW, ROWS_NO_ROW};
+    uint64_t total = 0;
+    HIPCHK(hipMemcpyAsync(err, d_err, 16, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipMemcpyAsync(&total, d_off + B, 8, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipStreamSynchronize(c->st));
+    if (err[0] != ROWS_NO_ROW) {
+        uint32_t len = 0;
+        HIPCHK(hipMemcpy(&len, d_lens + err[0], 4, hipMemcpyDeviceToHost));
+        snprintf(msg, sizeof msg, "rows: lens[%llu] is %u, above the row length %u", err[0], (unsigned)len, (unsigned)L);
+        return fail(BPE_GPU_EINVAL, msg);
+    }
+    if (err[1] != ROWS_NO_ROW) {
+        snprintf(msg, sizeof msg, "rows: row %llu keeps a cell outside 0 .. 2^32 - 1", err[1]);
+        return fail(BPE_GPU_EDATA, msg);
+    }
+    if ((r = dscratch(c, DS_ROWS_IDS, std::max<uint64_t>(total, 1) * 4, &d_ids))) return r;
+    if (total) {
+        if (cell_bytes == 4) rows_launch<uint32_t>(c, true, vec, grid, d_rows, B, L, stride, nullptr, d, d_skip, d_bounds, nullptr, nullptr, d_off, d_ids);
+        else rows_launch<int64_t>(c, true, vec, grid, d_rows, B, L, stride, nullptr, d, d_skip, d_bounds, nullptr, nullptr, d_off, d_ids);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(c->st));  // (the caller's rows are read no more)
+    }
+    c->rows_B = B;
+    c->rows_n = total;
+    c->rows_ready = true;
+    if (n) *n = (size_t)total;
+    return 0;
+}
+
+int bpe_gpu_fetch_rows(bpe_gpu_ctx *c, uint32_t *ids, size_t ids_cap, size_t *n, uint64_t *text_off, uint32_t *bounds,
+                       size_t B_cap, size_t *B) {
+    if (!c) return BPE_GPU_EINVAL;
+    if (!c->rows_ready) return fail(BPE_GPU_ESTATE, "fetch_rows: no rows: bpe_gpu_unpack_rows first");
+    if (n) *n = (size_t)c->rows_n;
+    if (B) *B = (size_t)c->rows_B;
+    if (ids && ids_cap < c->rows_n) return fail(BPE_GPU_EINVAL, "fetch_rows: ids_cap is below the ids");
+    if ((text_off || bounds) && B_cap < c->rows_B) return fail(BPE_GPU_EINVAL, "fetch_rows: B_cap is below the rows");
+    HIPCHK(hipSetDevice(c->dev));
+    int r;
+    if (ids && c->rows_n && (r = d2h_staged(c, ids, c->dscr[DS_ROWS_IDS], c->rows_n * 4))) return r;
+    if (text_off && (r = d2h_staged(c, text_off, c->dscr[DS_ROWS_OFF], (c->rows_B + 1) * 8))) return r;
+    if (bounds && c->rows_B && (r = d2h_staged(c, bounds, c->dscr[DS_ROWS_BOUNDS], c->rows_B * 8))) return r;
+    return 0;
+}
+
+int bpe_gpu_decode_rows(bpe_gpu_ctx *c, const uint32_t *pairs, size_t n_merges, const bpe_gpu_specials *specials,
+                        const bpe_gpu_vocab *vocab, uint8_t *out, size_t cap, size_t *out_len, uint64_t *byte_off) {
+    if (!c || !out_len || (!pairs && n_merges)) return BPE_GPU_EINVAL;
+    if (!c->rows_ready) return fail(BPE_GPU_ESTATE, "decode_rows: no rows: bpe_gpu_unpack_rows first");
+    char msg[400];
+    int r;
+    if (specials && bpe_specials_check(specials, msg, sizeof msg)) return fail(BPE_GPU_EINVAL, msg);
+    if (vocab) {  // (as bpe_gpu_decode_docs_vocab)
+        if ((r = bpe_vocab_check(vocab, pairs, n_merges, msg, sizeof msg))) return fail(r, r == BPE_GPU_EINVAL ? msg : "decode_rows: out of memory");
+        if ((specials ? specials->count : 0) != vocab->n_specials)
+            return fail(BPE_GPU_EINVAL, "decode_rows: the vocabulary's special count is not the set's");
+    }
+    const size_t len = (size_t)c->rows_n, B = (size_t)c->rows_B;
+    if ((r = decode_core(c, (const uint32_t *)c->dscr[DS_ROWS_IDS], hipMemcpyDeviceToDevice, len, pairs, n_merges, specials, out, cap,
+                         out_len, vocab)))
+        return r;
+    if (!byte_off) return 0;
+    // byte_off[k] = the ids' expansion-length prefix sum (scratch slot DS_DEC_OFF) at text_off[k], as decode_docs_run picks it
+    uint64_t *d_out;
+    if ((r = dscratch(c, DS_DD_BYTEOFF, (B + 1) * 8, &d_out))) return r;
+    k_ed_pick<<<(uint32_t)((B + 256) / 256), 256, 0, c->st>>>((const uint64_t *)c->dscr[DS_DEC_OFF], (const uint64_t *)c->dscr[DS_ROWS_OFF], B + 1, d_out);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(byte_off, d_out, (B + 1) * 8, hipMemcpyDeviceToHost, c->st));
     HIPCHK(hipStreamSynchronize(c->st));
     return 0;
 }

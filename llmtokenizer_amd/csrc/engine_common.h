@@ -681,6 +681,15 @@ enum DScr {
     DS_SPN_OUT,          // bpe_gpu_token_spans: the spans [ids][2]; stays with the ids
     DS_SPN_PACK,         // bpe_gpu_pack_spans: the rows of a call with a host pointer
     DS_STR_PACK,         // bpe_gpu_pack_stream: rows, seg and pos of a call with host pointers
+    DS_ROWS_IN,          // bpe_gpu_unpack_rows: the rows of a call with a host pointer
+    DS_ROWS_LENS,        // bpe_gpu_unpack_rows: ... and its lens
+    DS_ROWS_SKIP,        // bpe_gpu_unpack_rows: the sorted skip list, filled up to a power of two
+    DS_ROWS_BOUNDS,      // bpe_gpu_unpack_rows: (a, z) of every row [B][2]; stays until the next unpack
+    DS_ROWS_CNT,         // bpe_gpu_unpack_rows: the kept cells of every row [B + 1]
+    DS_ROWS_OFF,         // bpe_gpu_unpack_rows: text_off, their scan [B + 1]; stays until the next unpack
+    DS_ROWS_TMP,         // bpe_gpu_unpack_rows: rocprim temporary of that scan
+    DS_ROWS_IDS,         // bpe_gpu_unpack_rows: the kept ids; stays until the next unpack (bpe_gpu_decode_rows copies them)
+    DS_ROWS_ERR,         // bpe_gpu_unpack_rows: the two error words
     DS_COUNT
 };
 // bpe_gpu_train_split takes its eight token-sized arrays as one run of slots

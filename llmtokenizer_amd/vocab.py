@@ -489,14 +489,14 @@ class Tokenizer:
         span_rows = torch.empty((n_texts, int(max_length), 2), dtype=torch.int32, device=dev)
         return out + (e.pack_spans(max_length, truncation_side, out=span_rows),)
 
-    def _special_id(self, tok, what):
+    def _special_id(self, tok, what, fn="encode_packed"):
         """the id of a BOS / EOS argument: None, an int (a vocabulary id) or the name of one of vocab.specials"""
         if tok is None or isinstance(tok, (int, np.integer)):
             return None if tok is None else int(tok)
         name = tok.encode("utf-8") if isinstance(tok, str) else bytes(tok)
         specials = [bytes(s) for s in self.vocab.specials]
         if name not in specials:
-            raise BpeError(f"encode_packed: {what} {tok!r} is none of the vocabulary's specials")
+            raise BpeError(f"{fn}: {what} {tok!r} is none of the vocabulary's specials")
         return int(self.vocab.special_ids[specials.index(name)])
 
     def encode_packed(self, texts, seq_len, pad_id, bos=None, eos=None, drop_last=False, return_segments=False,
@@ -534,6 +534,32 @@ class Tokenizer:
         out = e.pack_stream(seq_len, pad_id, bos_id, eos_id, drop_last,
                             out=(new(), new() if return_segments else None, new() if return_positions else None))
         return tuple(t for t in out if t is not None) + (N,)
+
+    def decode_rows(self, rows, lens=None, pad_id=None, eos=None, skip_specials=False, return_bounds=False):
+        """The texts of a [B, L] grid of ids as a model hands it back: a list of B bytes objects (NUL bytes dropped, as
+        decode does).  rows: a 2-D numpy array of uint32, int32, int64 or uint64, or a torch tensor of int32 or int64
+        on the tokenizer's device with stride(1) == 1 and stride(0) >= shape[1], such as out[:, P:] of what generate
+        returned: it is read where it lies and no id passes through the host (Engine.unpack_rows; the contract:
+        bpe_gpu.h, "Rows back to texts").  Row k's window is its first lens[k] cells (lens None: the whole row).  Its
+        text begins behind the leading cells equal to pad_id (None: at the first cell) and ends before the first cell
+        that is an eos id or pad_id, or at the window's end; so left-padded rows with pad_id == eos read as they are
+        meant, and a text whose first token is the pad id loses it.  eos: None, an int (a vocabulary id), the name of
+        one of vocab.specials (str or bytes), or a list of up to 8 of them.  skip_specials: the ids of vocab.specials
+        are left out of the text.  A cell outside the text is never judged, whatever it holds; an id inside it that
+        the vocabulary does not hold raises BpeError.  return_bounds: also bounds uint32[B, 2], every row's (start,
+        end) in cells: end - start is the length of what the row generated."""
+        many = isinstance(eos, (list, tuple)) or (isinstance(eos, np.ndarray) and eos.ndim)
+        stops = [self._special_id(t, "eos", "decode_rows") for t in (eos if many else [eos]) if t is not None]
+        if hasattr(rows, "data_ptr"):  # a torch tensor
+            import torch
+            if not torch.cuda.is_available():  # (see encode_batch)
+                raise BpeError("decode_rows: a torch tensor: torch sees no GPU; import torch before the first "
+                               "call into llmtokenizer_amd, so that both share one HIP runtime")
+        e, v = self._eng(), self.vocab
+        B, _ = e._unpack_rows(rows, lens, pad_id, stops, v.special_ids if skip_specials else None)
+        out, bo = e.decode_rows(v.merges, v.specials or None, vocab=v)
+        texts = [out[int(bo[k]):int(bo[k + 1])] for k in range(B)]
+        return (texts, e.fetch_rows()[2]) if return_bounds else texts
 
     def decode_batch(self, ids, text_off):
         """the inverse of encode_batch(texts): the list of the texts' bytes (NUL bytes dropped, as decode does)"""
