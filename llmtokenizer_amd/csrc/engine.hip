@@ -2010,8 +2010,8 @@ int init_sort(bpe_gpu_ctx *c, const std::vector<uint32_t> &bh, std::vector<uint3
         c->stats.ms_count_pass = 0;
         if (!span) c->stats.count_pass_span = 0;
         c->prof_ms = -1.0;  // (the count pass's time, unless a later profile replaces it)
-        // 1 B/token read (V = 256: re-read once per bin part); tok[] was
-        // written by init_presence's streaming pass
+        // 1 B/token read (V = 256: re-read once per bin part); tok[] is
+        // written by k_sort_a
         c->prof_bytes = (double)c->n0 * (span ? 1 : parts);
         c->prof_launches = 1;
         const uint32_t per = (ntl + COLSCAN_GROUPS - 1) / COLSCAN_GROUPS;

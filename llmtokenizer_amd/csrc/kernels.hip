@@ -2944,8 +2944,9 @@ __global__ __launch_bounds__(SORT_T) __attribute__((amdgpu_waves_per_eu(SORT_A_W
     }
     __syncthreads();
     const uint64_t n0 = E->n0, nwords = (n0 + 3) / 4;
-    // pair positions [s, e); token positions [s, te) (the last tile owns n0 - 1)
-    const uint64_t s = (uint64_t)t * tile, e = min(n0 - 1, s + tile), te = min(n0, s + tile);
+    // pair positions [s, e); token positions [s, te): the last tile owns n0 - 1, which lies one past its
+    // pair positions when n0 - 1 is a multiple of the tile (one more round, without entries, writes it)
+    const uint64_t s = (uint64_t)t * tile, e = min(n0 - 1, s + tile), te = t + 1 == gridDim.x ? n0 : s + tile;
     const uint64_t gs = (uint64_t)(t / G) * G * tile;  // the tile group's first position (pass B's unit)
     const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const uint32_t *src = reinterpret_cast<const uint32_t *>(E->bytes);
