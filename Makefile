@@ -51,7 +51,7 @@ COBJ_STREAM := $(patsubst $(PKG)/src/%.c,$(BUILD)/%.o,$(CSRC_STREAM))
 # engine call, so tests/asan_rows needs no model)
 CSRC_ROWS := $(PKG)/src/bpe_rows.c
 COBJ_ROWS := $(patsubst $(PKG)/src/%.c,$(BUILD)/%.o,$(CSRC_ROWS))
-HIPDEPS := $(wildcard $(PKG)/csrc/*.hip $(PKG)/csrc/*.h) $(PKG)/src/bpe_split_presets.h include/bpe_gpu.h
+HIPDEPS := $(wildcard $(PKG)/csrc/*.hip $(PKG)/csrc/*.h) $(PKG)/src/bpe_split_presets.h $(PKG)/src/bpe_o200k_rule.h include/bpe_gpu.h
 
 all: $(PKG)/libbpe_amd.so tools/bpe_main oracle
 
@@ -61,7 +61,7 @@ $(BUILD):
 $(BUILD)/engine.o: $(HIPDEPS) | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $(PKG)/csrc/engine.hip -o $@
 
-$(BUILD)/%.o: $(PKG)/src/%.c $(wildcard include/*.h $(PKG)/src/*.h $(PKG)/csrc/unicode_classes.h) | $(BUILD)
+$(BUILD)/%.o: $(PKG)/src/%.c $(wildcard include/*.h $(PKG)/src/*.h $(PKG)/csrc/unicode_classes.h $(PKG)/csrc/unicode_case_classes.h) | $(BUILD)
 	$(CC) $(CFLAGS) -c $< -o $@
 
 $(PKG)/libbpe_amd.so: $(BUILD)/engine.o $(COBJ) $(COBJ_GPU) $(COBJ_TS) $(COBJ_SP) $(COBJ_SPECIAL) $(COBJ_VOCAB) $(COBJ_TEXTS) $(COBJ_SPANS) $(COBJ_STREAM) $(COBJ_ROWS)
@@ -133,7 +133,7 @@ asan-special: tests/asan_special/asan_special
 # BPE_SPLIT_GPT2_UNICODE's host code (the class table, the rule in src/bpe_split_preset.c and the preset through
 # src/bpe_special.c) the same way, in a stand-alone program that calls no engine function
 # (tests/asan_split_unicode/asan_split_unicode.c); run by tests/test_asan_split_unicode.py
-tests/asan_split_unicode/asan_split_unicode: tests/asan_split_unicode/asan_split_unicode.c $(CSRC_SPECIAL) $(CSRC_SP) $(wildcard include/*.h $(PKG)/src/*.h $(PKG)/csrc/unicode_classes.h)
+tests/asan_split_unicode/asan_split_unicode: tests/asan_split_unicode/asan_split_unicode.c $(CSRC_SPECIAL) $(CSRC_SP) $(wildcard include/*.h $(PKG)/src/*.h $(PKG)/csrc/unicode_classes.h $(PKG)/csrc/unicode_case_classes.h)
 	$(CC) -O1 -g -std=c11 -D_GNU_SOURCE -fno-omit-frame-pointer -fsanitize=address,undefined \
 	    -fno-sanitize-recover=undefined -Iinclude -o $@ tests/asan_split_unicode/asan_split_unicode.c $(CSRC_SPECIAL) $(CSRC_SP) -lm
 
@@ -143,7 +143,7 @@ asan-split-unicode: tests/asan_split_unicode/asan_split_unicode
 # BPE_SPLIT_CL100K's host code (the rule in src/bpe_split_preset.c and the preset through src/bpe_special.c) the
 # same way, in a stand-alone program that calls no engine function (tests/asan_split_cl100k/asan_split_cl100k.c);
 # run by tests/test_asan_split_cl100k.py
-tests/asan_split_cl100k/asan_split_cl100k: tests/asan_split_cl100k/asan_split_cl100k.c $(CSRC_SPECIAL) $(CSRC_SP) $(wildcard include/*.h $(PKG)/src/*.h $(PKG)/csrc/unicode_classes.h)
+tests/asan_split_cl100k/asan_split_cl100k: tests/asan_split_cl100k/asan_split_cl100k.c $(CSRC_SPECIAL) $(CSRC_SP) $(wildcard include/*.h $(PKG)/src/*.h $(PKG)/csrc/unicode_classes.h $(PKG)/csrc/unicode_case_classes.h)
 	$(CC) -O1 -g -std=c11 -D_GNU_SOURCE -fno-omit-frame-pointer -fsanitize=address,undefined \
 	    -fno-sanitize-recover=undefined -Iinclude -o $@ tests/asan_split_cl100k/asan_split_cl100k.c $(CSRC_SPECIAL) $(CSRC_SP) -lm
 

@@ -74,7 +74,7 @@ uint32_t *bpe_encode_split(const uint8_t *bytes, size_t n, const uint8_t *cls, c
 dyn_arr_t *bpe_train_split(const uint8_t *bytes, size_t n, const uint8_t *cls, const uint16_t *brk, long max_merges,
                            int device);
 
-/* The preset split rules (bpe_gpu.h: BPE_SPLIT_LINES, BPE_SPLIT_WORDS, BPE_SPLIT_GPT2, BPE_SPLIT_GPT2_UNICODE, BPE_SPLIT_CL100K) in plain C, on
+/* The preset split rules (bpe_gpu.h: BPE_SPLIT_LINES, BPE_SPLIT_WORDS, BPE_SPLIT_GPT2, BPE_SPLIT_GPT2_UNICODE, BPE_SPLIT_CL100K, BPE_SPLIT_O200K) in plain C, on
  * the host and without a GPU: the written definition bpe_gpu_split_preset is held to, and the
  * yardstick for inputs too large for a regular-expression engine.  Two-phase like the fetch calls:
  * out may be NULL, *count = pieces + 1 (the piece starts followed by n; n == 0: the single offset 0),
@@ -87,6 +87,11 @@ int bpe_split_offsets_host(int preset, const uint8_t *bytes, size_t n, uint64_t 
  * *digest = the FNV-1a 64 of the 0x110000 classes as bytes in code point order; either may be NULL.  Returns 0. */
 int bpe_unicode_class(uint32_t cp);
 int bpe_unicode_info(const char **source, uint64_t *digest);
+/* The case classes of BPE_SPLIT_O200K (bpe_gpu.h), pure host functions.  bpe_unicode_case_class: 1 U (\p{Lu}
+ * \p{Lt}), 2 l (\p{Ll}), 3 B (\p{Lm} \p{Lo}), 4 M (\p{M}), 0 every other code point and every value above
+ * U+10FFFF.  bpe_unicode_case_info: as bpe_unicode_info, for the second table (csrc/unicode_case_classes.h). */
+int bpe_unicode_case_class(uint32_t cp);
+int bpe_unicode_case_info(const char **source, uint64_t *digest);
 
 /* bpe_encode_split with a preset in place of the tables (bpe_gpu_split_preset): the way to
  * BPE_SPLIT_GPT2, which no two tables express.  Results and ownership as bpe_encode_split. */

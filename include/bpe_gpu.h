@@ -357,8 +357,54 @@ int bpe_gpu_docs_window(const uint64_t *doc_off, size_t ndocs, uint64_t n,
  * (A) back through a run of R, (B) ahead through white space.  The rest depends
  * on b[i - 8 .. i + 7] and n.  Where this formulation and the regular expression
  * disagree the expression is the definition.  bpe_ex.h's bpe_split_offsets_host
- * is this rule in plain C, one pass from the left.  o200k's pattern (case classes)
- * is another pattern and not offered.
+ * is this rule in plain C, one pass from the left.
+ *
+ * BPE_SPLIT_O200K is the pre-tokenizer of o200k_base (no table rule either).  Its
+ * pieces are the successive matches of
+ *   [^\r\n\p{L}\p{N}]?[\p{Lu}\p{Lt}\p{Lm}\p{Lo}\p{M}]*[\p{Ll}\p{Lm}\p{Lo}\p{M}]+(?i:'s|'t|'re|'ve|'m|'ll|'d)?
+ *   |[^\r\n\p{L}\p{N}]?[\p{Lu}\p{Lt}\p{Lm}\p{Lo}\p{M}]+[\p{Ll}\p{Lm}\p{Lo}\p{M}]*(?i:'s|'t|'re|'ve|'m|'ll|'d)?
+ *   |\p{N}{1,3}| ?[^\s\p{L}\p{N}]+[\r\n/]*|\s*[\r\n]+|\s+(?!\S)|\s+
+ * (one pattern), found and reported as BPE_SPLIT_CL100K's are, over the same
+ * characters, with the same fold for the contractions.  A character has a kind:
+ * U (\p{Lu} \p{Lt}), l (\p{Ll}), B (\p{Lm} \p{Lo}), M (\p{M}) -- the case
+ * classes of a second table (bpe_ex.h bpe_unicode_case_class) --, N, R (\r \n),
+ * W (the other White_Space, S among them), SL the '/', AP the apostrophe and P the
+ * rest; "letter" is U, l, B or M and "ws" is R or W.  The rule is an automaton
+ * (src/bpe_o200k_rule.h states it in C).  Its state, after a character: FRESH,
+ * nothing is carried; UB / LB, inside the letters of a word before / after its
+ * first l; C, inside the letters of a contraction; N1 / N2, one / two numbers of a
+ * piece so far; PU, inside the body of a punctuation piece; PT, inside its tail
+ * [\r\n/]*.  Before the text the state is FRESH and everything reads as R; past
+ * its end everything reads as S.  Character 0 starts a piece.  Per character c
+ * with p the one before and x the one after, in state s:
+ *   c is a letter, s is C: no start; the next state is FRESH when c ends the
+ *     contraction (p is AP and c folds to s t m d, or the character before p is AP
+ *     and p c fold to re ve ll), else C.
+ *   c is M, s is PU: no start, PU (the punctuation piece takes it).
+ *   c is any other letter: a start when s is LB and c is U; when s is UB, c is U,
+ *     p is B or M and only U lie between c and the first character after it that
+ *     is no letter (the expression gives the word's last B or M to [..]+ and
+ *     starts again); when s is FRESH and p is not W (a W is the word's first
+ *     character); when s is N1, N2, PU or PT.  Next: UB for U, LB for l; B and M
+ *     keep LB when they did not start and are UB otherwise.
+ *   c is N: a start unless s is N1 or N2; next N1, N2 (after N1), FRESH (after N2).
+ *   c is R: a start when p is no ws and s is neither PU nor PT; next PT after PU
+ *     or PT (the tail), else FRESH.
+ *   c is W: next FRESH.  A start when p is no ws; when x is no ws; when p is R and
+ *     no R follows in this white-space run; when p is R and s is PT.
+ *   c is P, SL or AP: when c is AP, s is UB or LB and the letters of a contraction
+ *     follow (x folds to s t m d, or x and the character after it to re ve ll):
+ *     no start, C.  Else when s is PU, or s is PT and c is SL: no start, same
+ *     state.  Else a start, unless s is FRESH and p is S (the space before
+ *     punctuation is the piece's first character); the next state is UB when c
+ *     started and x is a letter (c is the word's first character), else PU.
+ * With specials a byte of a match sends every state to FRESH and reads as R.
+ * Two conditions read ahead through runs of any length (only U up to the end of the
+ * letter run, an R later in the white-space run); everything else a run of any
+ * length decides is in the state.  Where this formulation and the regular
+ * expression disagree the expression is the definition.  bpe_ex.h's
+ * bpe_split_offsets_host is this rule in plain C: a pass from the right for the
+ * two conditions, then the automaton from the left.
  *
  * The offsets belong to the loaded bytes.  bpe_gpu_load / _load_fd / _synth /
  * _trim, bpe_gpu_train / _train_ex and a sharded group's load, synth and train
@@ -367,20 +413,20 @@ int bpe_gpu_docs_window(const uint64_t *doc_off, size_t ndocs, uint64_t n,
  * bpe_gpu_split replaces them.  A call that needs them and finds none returns
  * BPE_GPU_ESTATE.
  * ---------------------------------------------------------------------- */
-enum { BPE_SPLIT_LINES = 0, BPE_SPLIT_WORDS = 1, BPE_SPLIT_GPT2 = 2, BPE_SPLIT_GPT2_UNICODE = 4, BPE_SPLIT_CL100K = 6 }; /* (3 and 5 are no presets) */
+enum { BPE_SPLIT_LINES = 0, BPE_SPLIT_WORDS = 1, BPE_SPLIT_GPT2 = 2, BPE_SPLIT_GPT2_UNICODE = 4, BPE_SPLIT_CL100K = 6, BPE_SPLIT_O200K = 8 }; /* (3, 5 and 7 are no presets) */
 /* bytes one workgroup of the split kernels handles per step, and the largest grid
    (a corpus of more than TILE * GRID bytes is walked in grid strides) */
 #define BPE_GPU_SPLIT_TILE 4096
 #define BPE_GPU_SPLIT_GRID 2048
-/* fill cls[256] / brk[16] with a table preset (pure function, no GPU); BPE_SPLIT_GPT2, BPE_SPLIT_GPT2_UNICODE and
-   BPE_SPLIT_CL100K have no tables: BPE_GPU_EINVAL */
+/* fill cls[256] / brk[16] with a table preset (pure function, no GPU); BPE_SPLIT_GPT2, BPE_SPLIT_GPT2_UNICODE,
+   BPE_SPLIT_CL100K and BPE_SPLIT_O200K have no tables: BPE_GPU_EINVAL */
 int bpe_gpu_split_rule(int preset, uint8_t *cls, uint16_t *brk);
 /* out4 = {BPE_GPU_SPLIT_TILE, BPE_GPU_SPLIT_TILE * BPE_GPU_SPLIT_GRID, 0, 0} (pure function, no GPU) */
 int bpe_gpu_split_info(uint64_t *out4);
 /* split the loaded bytes; *ndocs = pieces.  A cls entry above 15 is BPE_GPU_EINVAL. */
 int bpe_gpu_split(bpe_gpu_ctx *ctx, const uint8_t *cls, const uint16_t *brk, size_t *ndocs);
 /* the same by a preset: BPE_SPLIT_LINES / BPE_SPLIT_WORDS are bpe_gpu_split with their tables, BPE_SPLIT_GPT2,
-   BPE_SPLIT_GPT2_UNICODE and BPE_SPLIT_CL100K mark the starts with kernels of their own; the offsets and all that is said of them above are the same.
+   BPE_SPLIT_GPT2_UNICODE, BPE_SPLIT_CL100K and BPE_SPLIT_O200K mark the starts with kernels of their own; the offsets and all that is said of them above are the same.
    BPE_GPU_EINVAL for another preset, BPE_GPU_ESTATE before a load. */
 int bpe_gpu_split_preset(bpe_gpu_ctx *ctx, int preset, size_t *ndocs);
 /* the last split's offsets; out may be NULL, *count = ndocs + 1 */

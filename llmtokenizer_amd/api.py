@@ -172,13 +172,13 @@ def encode_batch(docs, merges, device=0):
     return _take_ids(p, n.value), offsets
 
 
-# bpe_gpu.h BPE_SPLIT_LINES / BPE_SPLIT_WORDS / BPE_SPLIT_GPT2 / BPE_SPLIT_GPT2_UNICODE / BPE_SPLIT_CL100K (3 and 5 are no presets)
-SPLIT_PRESETS = {"lines": 0, "words": 1, "gpt2": 2, "gpt2_unicode": 4, "cl100k": 6}
+# bpe_gpu.h BPE_SPLIT_LINES / BPE_SPLIT_WORDS / BPE_SPLIT_GPT2 / BPE_SPLIT_GPT2_UNICODE / BPE_SPLIT_CL100K / BPE_SPLIT_O200K (3, 5 and 7 are no presets)
+SPLIT_PRESETS = {"lines": 0, "words": 1, "gpt2": 2, "gpt2_unicode": 4, "cl100k": 6, "o200k": 8}
 TABLE_PRESETS = ("lines", "words")  # the presets two tables express
 
 
 def _no_tables(rule):
-    """is rule the name of a preset without tables ("gpt2", "gpt2_unicode", "cl100k": the preset calls run them)?"""
+    """is rule the name of a preset without tables ("gpt2", "gpt2_unicode", "cl100k", "o200k": the preset calls run them)?"""
     return isinstance(rule, str) and rule in SPLIT_PRESETS and rule not in TABLE_PRESETS
 
 
@@ -189,6 +189,15 @@ def unicode_class(cp):
     """The class of code point cp under "gpt2_unicode" (bpe_ex.h bpe_unicode_class): "L" \\p{L}, "N" \\p{N},
     "S" U+0020, "W" the other White_Space, "P" the rest (and everything above U+10FFFF).  No GPU."""
     return UNICODE_CLASSES[_lib.load().bpe_unicode_class(int(cp))]
+
+
+UNICODE_CASE_CLASSES = ("O", "U", "l", "B", "M")
+
+
+def unicode_case_class(cp):
+    """The case class of code point cp under "o200k" (bpe_ex.h bpe_unicode_case_class): "U" \\p{Lu} \\p{Lt},
+    "l" \\p{Ll}, "B" \\p{Lm} \\p{Lo}, "M" \\p{M}, "O" the rest (and everything above U+10FFFF).  No GPU."""
+    return UNICODE_CASE_CLASSES[_lib.load().bpe_unicode_case_class(int(cp))]
 
 
 def unicode_info():
@@ -203,7 +212,7 @@ def split_rule(preset):
     """The tables (cls uint8[256], brk uint16[16]) of a preset split rule, "lines"
     or "words" (bpe_gpu.h bpe_gpu_split_rule; this project's rules, not GPT-2's
     regular expression): a piece starts at byte i when bit cls[b[i]] of
-    brk[cls[b[i - 1]]] is set, and at byte 0.  "gpt2", "gpt2_unicode" and "cl100k" have no
+    brk[cls[b[i - 1]]] is set, and at byte 0.  "gpt2", "gpt2_unicode", "cl100k" and "o200k" have no
     tables (a start there depends on six and fifteen bytes): pass the name to
     split / encode_split / train_split / split_host."""
     if _no_tables(preset):
@@ -274,7 +283,7 @@ def split_host_special(data: bytes, rule, specials):
 
 def split_host(data: bytes, rule, specials=None):
     """The offsets (uint64: the piece starts followed by len(data)) of a preset
-    rule, "lines", "words", "gpt2", "gpt2_unicode" or "cl100k", computed on the host in plain C
+    rule, "lines", "words", "gpt2", "gpt2_unicode", "cl100k" or "o200k", computed on the host in plain C
     (bpe_ex.h bpe_split_offsets_host): the definition Engine.split(rule) is held
     to.  With specials (a list of bytes-like objects, see check_specials) the
     definition of Engine.split(rule, specials), for a preset or a (cls, brk)
@@ -322,7 +331,7 @@ def _rule_tables(rule):
 
 def encode_split(data: bytes, merges, rule="words", device=0, specials=None):
     """Split data into pieces on the GPU (rule: a preset name, "lines", "words",
-    "gpt2", "gpt2_unicode" or "cl100k" (the pre-tokenizer of cl100k_base and Llama 3), or a (cls, brk) pair, see
+    "gpt2", "gpt2_unicode", "cl100k" (the pre-tokenizer of cl100k_base and Llama 3) or "o200k" (that of o200k_base), or a (cls, brk) pair, see
     split_rule) and encode the pieces as documents.  Returns (ids,
     id_offsets, byte_offsets), both offsets uint64 of length pieces + 1: piece d
     is data[byte_offsets[d]:byte_offsets[d + 1]] and its ids are
@@ -1033,7 +1042,7 @@ class Engine:
 
     def split(self, rule="words", specials=None):
         """split the resident bytes into pieces on the device (rule: a preset
-        name, "lines", "words", "gpt2", "gpt2_unicode" or "cl100k", or a (cls, brk) pair, see split_rule); the offsets stay in HBM for
+        name, "lines", "words", "gpt2", "gpt2_unicode", "cl100k" or "o200k", or a (cls, brk) pair, see split_rule); the offsets stay in HBM for
         encode_split().  With specials (a list of bytes-like objects, see check_specials) every occurrence of
         one is a piece of its own (bpe_gpu_split_special); they last as long as the offsets, and a split
         without them forgets them.  Returns the number of pieces."""

@@ -28,6 +28,7 @@
 #include "encode_win.hip"
 #include "encode_docs.hip"
 #include "split.hip"
+#include "split_o200k.hip"
 #include "train_split.hip"
 #include "special.hip"
 #include "vocab.hip"

@@ -662,8 +662,8 @@ enum DScr {
     DS_SP_REMOVED_SCAN,  // ... and their scan
     DS_SP_DEC_BYTES,     // decode_run: the specials' bytes
     DS_SP_DEC_OFF,       // decode_run: ... and offsets
-    DS_CL_CHAINS,        // mark_cl100k: the wave tiles' chain effects and their scan
-    DS_CL_TMP,           // mark_cl100k: rocprim temporary of that scan
+    DS_CL_CHAINS,        // mark_cl100k, mark_o200k: the wave tiles' chain effects and their scan
+    DS_CL_TMP,           // mark_cl100k, mark_o200k: rocprim temporary of that scan
     DS_VOC_FWD,          // bpe_gpu_map_ids: the forward table, internal id -> vocabulary id
     DS_VOC_INV,          // decode_run: the inverse table of bpe_gpu_decode_docs_vocab
     DS_VOC_ERR,          // bpe_gpu_map_ids: error word

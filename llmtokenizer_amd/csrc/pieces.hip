@@ -24,11 +24,11 @@ static int grow_array(bpe_gpu_ctx *c, void **p, size_t *cap, size_t need, size_t
 // ------------------------------------------------ pieces of the resident bytes (split.hip)
 
 // What marks the starts: the tables of bpe_gpu_split, or the kernel of a preset that has none.
-enum MarkKind { MARK_TABLE, MARK_GPT2, MARK_GPT2_UNICODE, MARK_CL100K };
+enum MarkKind { MARK_TABLE, MARK_GPT2, MARK_GPT2_UNICODE, MARK_CL100K, MARK_O200K };
 struct Marker {
     MarkKind kind = MARK_TABLE;
     SplitRule tables;  // kind == MARK_TABLE
-    bool specials_first() const { return kind == MARK_CL100K; }  // found before marking: the kernel reads their cover
+    bool specials_first() const { return kind == MARK_CL100K || kind == MARK_O200K; }  // found before marking: the kernel reads their cover
     // what k_sp_patch decides again around a match: 1 BPE_SPLIT_GPT2's rule, 2 BPE_SPLIT_GPT2_UNICODE's, 0 nothing
     int patch_mode() const { return kind == MARK_GPT2 ? 1 : kind == MARK_GPT2_UNICODE ? 2 : 0; }
 };
@@ -41,6 +41,7 @@ static int marker_of(int preset, const uint8_t *cls, const uint16_t *brk, Marker
     case BPE_SPLIT_GPT2: m->kind = MARK_GPT2; return 0;
     case BPE_SPLIT_GPT2_UNICODE: m->kind = MARK_GPT2_UNICODE; return 0;
     case BPE_SPLIT_CL100K: m->kind = MARK_CL100K; return 0;
+    case BPE_SPLIT_O200K: m->kind = MARK_O200K; return 0;
     default:  // a table preset (bpe_gpu_split_rule refuses every other number), or the caller's tables
         if (preset >= 0 && bpe_gpu_split_rule(preset, pc, pb)) return BPE_GPU_EINVAL;
         if (preset >= 0) cls = pc, brk = pb;
@@ -134,6 +135,24 @@ static int mark_cl100k(bpe_gpu_ctx *c, const uint32_t *cover, uint64_t n, uint64
     return 0;
 }
 
+// BPE_SPLIT_O200K's marks (split_o200k.hip): the maps of the wave tiles on the rule's automaton from the left and,
+// behind a reset, from the right, one scan of them, and the marks.  The slots are mark_cl100k's, which never
+// runs in the same split.  cover: the specials' bitmap, or nullptr
+static int mark_o200k(bpe_gpu_ctx *c, const uint32_t *cover, uint64_t n, uint64_t ntiles, uint64_t nwt, uint32_t grid,
+                      uint16_t *mask, uint32_t *wcnt) {
+    static const O2Table T = o2_table();
+    int r;
+    uint64_t *sum;
+    const size_t cnt = 2 * nwt + 1;
+    if ((r = dscratch(c, DS_CL_CHAINS, 2 * cnt * 8, &sum))) return r;
+    uint64_t *in = sum + cnt;
+    k_o2_summary<<<grid, SP_T, 0, c->st>>>(c->h.bytes, n, ntiles, cover, T, sum);
+    HIPCHK(hipGetLastError());
+    if ((r = ROCPRIM_RUN(c, DS_CL_TMP, rocprim::exclusive_scan(tmp, tb, sum, in, O2_TO_FRESH, cnt, O2Compose(), c->st)))) return r;
+    k_split_mark_o200k<<<grid, SP_T, 0, c->st>>>(c->h.bytes, n, ntiles, cover, T, in, mask, wcnt);
+    return 0;
+}
+
 // The body of bpe_gpu_split, bpe_gpu_split_preset and bpe_gpu_split_special (preset >= 0, or the tables): all but the
 // marking launches is one code, so the offsets and their lifetime are the same whichever kernel marked the starts.
 // sp: the specials of bpe_gpu_split_special (nullptr: none, and nothing but the launches below runs)
@@ -187,6 +206,9 @@ static int split_run(bpe_gpu_ctx *c, int preset, const uint8_t *cls, const uint1
             break;
         case MARK_CL100K:
             if ((r = mark_cl100k(c, F.cover, n, ntiles, nwt, grid, mask, wcnt))) return r;
+            break;
+        case MARK_O200K:
+            if ((r = mark_o200k(c, F.cover, n, ntiles, nwt, grid, mask, wcnt))) return r;
             break;
         }
         HIPCHK(hipGetLastError());

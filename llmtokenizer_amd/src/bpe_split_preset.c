@@ -1,12 +1,16 @@
 /*
  * bpe_split_preset.c -- the preset split rules of bpe_ex.h: the rules in plain C
  * (bpe_split_offsets_host: the written definition the device kernels are held
- * to, no GPU; BPE_SPLIT_CL100K among them), and bpe_encode_split_preset / bpe_train_split_preset over
+ * to, no GPU; BPE_SPLIT_CL100K and BPE_SPLIT_O200K among them), and bpe_encode_split_preset / bpe_train_split_preset over
  * bpe_gpu_split_preset, on the bodies bpe_encode_split and bpe_train_split run.
  */
 #include "bpe_internal.h"
 #include "bpe_split_presets.h"
+#include "bpe_o200k_rule.h"
 #include "../csrc/unicode_classes.h"
+#include "../csrc/unicode_case_classes.h"
+
+#include <stdlib.h>
 
 enum { C_P = 0, C_L = 1, C_N = 2, C_S = 3, C_W = 4 }; /* the classes of BPE_SPLIT_WORDS and BPE_SPLIT_GPT2 */
 
@@ -237,6 +241,102 @@ static void starts_cl100k(const uint8_t *b, size_t n, uint64_t *out, size_t cap,
     }
 }
 
+/* ---- BPE_SPLIT_O200K: the rule of bpe_gpu.h.  One pass from the right leaves what every character has to know
+ * of the text after it (o2_back), one pass from the left walks the automaton of bpe_o200k_rule.h. */
+
+static uint32_t ucc_code(uint32_t cp)
+{
+    return cp > 0x10FFFF ? 0u : (BPE_UCC_STAGE2[32u * BPE_UCC_STAGE1[cp >> 8] + ((cp >> 3) & 31u)] >> (4u * (cp & 7u))) & 15u;
+}
+
+int bpe_unicode_case_class(uint32_t cp)
+{
+    const uint32_t t = ucc_code(cp);
+    return t <= 4 ? (int)t : 0;
+}
+
+int bpe_unicode_case_info(const char **source, uint64_t *digest)
+{
+    if (source) *source = BPE_UCC_SOURCE;
+    if (digest) *digest = BPE_UCC_DIGEST;
+    return 0;
+}
+
+/* the kind (bpe_o200k_rule.h) of the character that begins at byte i < n, *end the offset just past it, *fold the
+ * letter a contraction reads there or 0, *space: it is U+0020 */
+static int o2_char(const uint8_t *b, size_t n, size_t i, size_t *end, int *fold, int *space)
+{
+    static const uint8_t kind_of[7] = {O2_P, O2_U, O2_LOW, O2_B, O2_M, O2_N, O2_W};
+    uint32_t cp = 0;
+    const int len = u8_seq(b, n, i, &cp);
+    *end = i + (len ? (size_t)len : 1);
+    *fold = 0;
+    *space = len && cp == ' ';
+    if (!len) return O2_P; /* a byte in no well-formed sequence */
+    if (cp == '\r' || cp == '\n') return O2_R;
+    if (cp == '/') return O2_SL;
+    if (cp == '\'') return O2_AP;
+    if (cp >= 'A' && cp <= 'Z') *fold = (int)cp + ('a' - 'A');
+    else if (cp >= 'a' && cp <= 'z') *fold = (int)cp;
+    else if (cp == 0x17F) *fold = 's';
+    return kind_of[ucc_code(cp)];
+}
+
+static int o2_one(int f) { return f == 's' || f == 't' || f == 'm' || f == 'd'; }
+static int o2_two(int f, int g) { return ((f == 'r' || f == 'v') && g == 'e') || (f == 'l' && g == 'l'); }
+static int o2_letter(int k) { return k == O2_U || k == O2_LOW || k == O2_B || k == O2_M; }
+
+/* the starts of text b[0 .. n) under BPE_SPLIT_O200K, in order: out[k] written below cap, *k their number */
+static int starts_o200k(const uint8_t *b, size_t n, uint64_t *out, size_t cap, size_t *k)
+{
+    if (!n) return 0;
+    uint8_t *back = malloc(n); /* per lead byte: the state of the chains read from the right, to its right */
+    if (!back) return BPE_GPU_ENOMEM;
+    size_t end;
+    int fold, space;
+    memset(back, O2_CONT, n); /* (the bytes inside a sequence) */
+    for (size_t i = 0; i < n; i = end) back[i] = (uint8_t)o2_char(b, n, i, &end, &fold, &space);
+    int right = O2_BACK_END;
+    for (size_t i = n; i-- > 0;) {
+        const int kd = back[i];
+        back[i] = (uint8_t)right;
+        right = o2_back(right, kd);
+    }
+    int st = O2_FRESH;
+    int pk = O2_R, ppk = O2_R, pf = 0, pspace = 0; /* the kinds of the two characters before, the fold and spaceness of the last */
+    for (size_t i = 0; i < n; i = end) {
+        size_t e2, e3;
+        int nf = 0, nnf = 0, ns, s;
+        const int kd = o2_char(b, n, i, &end, &fold, &space);
+        const int nk = end < n ? o2_char(b, n, end, &e2, &nf, &ns) : O2_W; /* past the end all reads as spaces */
+        if (end < n && e2 < n) (void)o2_char(b, n, e2, &e3, &nnf, &ns);
+        const int pws = pk == O2_W || pk == O2_R;
+        int sym = kd;
+        if (o2_letter(kd)) {
+            if ((pk == O2_AP && o2_one(fold)) || (ppk == O2_AP && o2_two(pf, fold))) sym |= O2_F0;
+            if (pk == O2_W) sym |= O2_F1;
+            if (kd == O2_U && (pk == O2_B || pk == O2_M) && (back[i] & 1)) sym |= O2_F2;
+        } else if (kd == O2_W) {
+            if (!pws || !(nk == O2_W || nk == O2_R) || (pk == O2_R && !(back[i] & 2))) sym |= O2_F0;
+            if (pk == O2_R) sym |= O2_F1;
+        } else if (kd == O2_R) {
+            if (!pws) sym |= O2_F0;
+        } else if (kd != O2_N) {
+            if (o2_letter(nk)) sym |= O2_F0;
+            if (pspace) sym |= O2_F1;
+            if (kd == O2_AP && (o2_one(nf) || o2_two(nf, nnf))) sym |= O2_F2;
+        }
+        st = o2_step(st, sym, &s);
+        if (s || i == 0) {
+            if (out && *k < cap) out[*k] = i;
+            ++*k;
+        }
+        ppk = pk, pk = kd, pf = fold, pspace = space;
+    }
+    free(back);
+    return 0;
+}
+
 static int starts_words(const uint8_t *b, size_t i)
 {
     const int c = class_of(b[i]), p = class_of(b[i - 1]);
@@ -248,8 +348,9 @@ int bpe_split_offsets_host(int preset, const uint8_t *bytes, size_t n, uint64_t 
     if ((!bytes && n) || !count) return BPE_GPU_EINVAL;
     if (!split_preset_find(preset)) return BPE_GPU_EINVAL;
     size_t k = 0;
-    if (preset == BPE_SPLIT_CL100K) {
-        starts_cl100k(bytes, n, out, cap, &k);
+    if (preset == BPE_SPLIT_CL100K || preset == BPE_SPLIT_O200K) {
+        if (preset == BPE_SPLIT_CL100K) starts_cl100k(bytes, n, out, cap, &k);
+        else if (starts_o200k(bytes, n, out, cap, &k)) return BPE_GPU_ENOMEM;
         if (out && k < cap) out[k] = n;
         *count = k + 1;
         return 0;

@@ -25,6 +25,7 @@ static inline const struct split_preset *split_preset_find(int preset)
         {BPE_SPLIT_GPT2, "BPE_SPLIT_GPT2", 0},
         {BPE_SPLIT_GPT2_UNICODE, "BPE_SPLIT_GPT2_UNICODE", 0},
         {BPE_SPLIT_CL100K, "BPE_SPLIT_CL100K", 0},
+        {BPE_SPLIT_O200K, "BPE_SPLIT_O200K", 0},
     };
     for (size_t k = 0; k < sizeof all / sizeof all[0]; k++)
         if (all[k].id == preset) return &all[k];

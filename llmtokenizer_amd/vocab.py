@@ -24,7 +24,12 @@ from ._lib import BpeError
 # the cl100k_base / Llama 3 pre-tokenization pattern (bpe_gpu.h BPE_SPLIT_CL100K)
 CL100K_PATTERN = (r"(?i:'s|'t|'re|'ve|'m|'ll|'d)|[^\r\n\p{L}\p{N}]?\p{L}+|\p{N}{1,3}| ?[^\s\p{L}\p{N}]+[\r\n]*"
                   r"|\s*[\r\n]+|\s+(?!\S)|\s+")
-RULES = ("gpt2_unicode", "cl100k")  # the presets a vocabulary file can name
+# the o200k_base pre-tokenization pattern (bpe_gpu.h BPE_SPLIT_O200K)
+O200K_PATTERN = (r"[^\r\n\p{L}\p{N}]?[\p{Lu}\p{Lt}\p{Lm}\p{Lo}\p{M}]*[\p{Ll}\p{Lm}\p{Lo}\p{M}]+(?i:'s|'t|'re|'ve|'m|'ll|'d)?"
+                 r"|[^\r\n\p{L}\p{N}]?[\p{Lu}\p{Lt}\p{Lm}\p{Lo}\p{M}]+[\p{Ll}\p{Lm}\p{Lo}\p{M}]*(?i:'s|'t|'re|'ve|'m|'ll|'d)?"
+                 r"|\p{N}{1,3}| ?[^\s\p{L}\p{N}]+[\r\n/]*|\s*[\r\n]+|\s+(?!\S)|\s+")
+SPLIT_PATTERNS = {"cl100k": CL100K_PATTERN, "o200k": O200K_PATTERN}  # the Split patterns a tokenizer.json can name
+RULES = ("gpt2_unicode", "cl100k", "o200k")  # the presets a vocabulary file can name
 ID_LIMIT = 1 << 24
 
 
@@ -212,8 +217,8 @@ class Vocab:
     @classmethod
     def from_tokenizer_json(cls, path):
         """read a byte-level BPE tokenizer.json.  The rule comes from its pre-tokenizer (ByteLevel with
-        use_regex: "gpt2_unicode"; Sequence[Split(the cl100k pattern, Isolated), ByteLevel(use_regex false)]:
-        "cl100k"), the specials from added_tokens.  Refused, by name: add_prefix_space, a normalizer,
+        use_regex: "gpt2_unicode"; Sequence[Split(the cl100k or the o200k pattern, Isolated), ByteLevel(use_regex
+        false)]: "cl100k" or "o200k"), the specials from added_tokens.  Refused, by name: add_prefix_space, a normalizer,
         byte_fallback, dropout, a subword prefix or suffix, an added token with lstrip / rstrip / single_word /
         normalized, any other pre-tokenizer or pattern, a model type other than BPE, and a vocabulary with a
         token its merges do not reach.  A post-processor (Llama 3's adds <|begin_of_text|>) is not applied:
@@ -261,7 +266,7 @@ class Vocab:
     def _rule_of(pt, where):
         def refuse(what):
             raise BpeError(f"{where}: {what}: pre-tokenizer {json.dumps(pt)} is not supported (ByteLevel with "
-                           f"use_regex, or Split on the cl100k pattern followed by ByteLevel without, are)")
+                           f"use_regex, or Split on the cl100k or the o200k pattern followed by ByteLevel without, are)")
 
         def byte_level(p, regex):
             if p.get("type") != "ByteLevel":
@@ -282,12 +287,13 @@ class Vocab:
                 refuse("a Sequence other than [Split, ByteLevel]")
             sp = seq[0]
             pattern = (sp.get("pattern") or {}).get("Regex")
-            if pattern != CL100K_PATTERN:
+            rule = next((r for r, p in SPLIT_PATTERNS.items() if p == pattern), None)
+            if rule is None:
                 refuse(f"the pattern {pattern!r}")
             if sp.get("behavior") != "Isolated" or sp.get("invert"):
                 refuse(f"Split with behavior {sp.get('behavior')!r}, invert {sp.get('invert')!r}")
             byte_level(seq[1], False)
-            return "cl100k"
+            return rule
         refuse(f"type {pt.get('type')!r}")
 
     @classmethod
@@ -356,7 +362,7 @@ class Vocab:
             pre = dict(byte_level, use_regex=True)
         else:
             pre = {"type": "Sequence", "pretokenizers": [
-                {"type": "Split", "pattern": {"Regex": CL100K_PATTERN}, "behavior": "Isolated", "invert": False},
+                {"type": "Split", "pattern": {"Regex": SPLIT_PATTERNS[self.rule]}, "behavior": "Isolated", "invert": False},
                 dict(byte_level, use_regex=False)]}
         tb = self.token_bytes()
         text = [_to_alphabet(t) for t in tb]

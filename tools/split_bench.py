@@ -10,8 +10,9 @@ marking kernels).  A third corpus, english_nonascii, is english_like with every
 --nonascii-th letter replaced by a two-byte Cyrillic letter (D0 B0..BF): the
 ASCII corpora take gpt2_unicode's all-ASCII path, this one its decoding path.
 Two more are one run each, for the rules whose starts depend on the position in
-a run ("cl100k"): digits (the ten digits over and over) and spaces_newline
-(spaces and one final newline).  --corpora selects among the five.
+a run ("cl100k", "o200k"): digits (the ten digits over and over) and spaces_newline
+(spaces and one final newline); and two for "o200k": capitals (capital letters and one
+final small one) and contractions ('s over and over).  --corpora selects among the seven.
 
   split    Engine.split(rule) alone, alternated with a device-to-device
            hipMemcpyAsync of the same number of bytes timed the same way (host
@@ -80,8 +81,8 @@ def nonascii(sample, every):
     return out
 
 
-NO_TABLES = ("gpt2", "gpt2_unicode", "cl100k")
-CORPORA = ("seed3", "english_like", "english_nonascii", "digits", "spaces_newline")
+NO_TABLES = ("gpt2", "gpt2_unicode", "cl100k", "o200k")
+CORPORA = ("seed3", "english_like", "english_nonascii", "digits", "spaces_newline", "capitals", "contractions")
 
 
 def med(xs):
@@ -169,10 +170,13 @@ def main():
         if corpus == "seed3":
             e.synth(3, n)
             host = None
-        elif corpus in ("digits", "spaces_newline"):  # one run as long as the text
-            host = np.tile(np.frombuffer(b"0123456789", np.uint8), n // 10 + 1)[:n] if corpus == "digits" else np.full(n, 0x20, np.uint8)
+        elif corpus in ("digits", "spaces_newline", "capitals", "contractions"):  # one run as long as the text
+            unit = {"digits": b"0123456789", "spaces_newline": b" ", "capitals": b"A", "contractions": b"'s"}[corpus]
+            host = np.tile(np.frombuffer(unit, np.uint8), n // len(unit) + 1)[:n].copy()
             if corpus == "spaces_newline":
                 host[-1] = 0x0A
+            if corpus == "capitals":  # ("o200k": the last letter decides whether the run before it is one piece)
+                host[-1] = ord("a")
             e.load(host.tobytes())
         else:
             part = sample if corpus == "english_like" else nonascii(sample, args.nonascii)
@@ -189,7 +193,7 @@ def main():
                 t1 = time.perf_counter()
                 t_split.append(t1 - t0)
                 t_copy.append(cp.run())
-            moved = n + n // 4 + 8 * (nd + 1) + 12 * (n // 1024) + (n + 16 * (n // 1024) if rule == "cl100k" else 0)
+            moved = n + n // 4 + 8 * (nd + 1) + 12 * (n // 1024) + (n + 16 * (n // 1024) if rule == "cl100k" else n + 32 * (n // 1024) if rule == "o200k" else 0)
             ms, mc = med(t_split), med(t_copy)
             rate = moved / (ms["ms_median"] * 1e-3) / 1e9
             copy_rate = 2 * n / (mc["ms_median"] * 1e-3) / 1e9
