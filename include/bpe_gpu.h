@@ -154,7 +154,11 @@ int bpe_gpu_fetch_events(bpe_gpu_ctx *ctx, uint64_t *out, size_t cap, size_t *co
 
 /* Free the context's device memory (buffer pool, corpus, scratch) but keep
    the stream, events and pinned host staging, so the next load on it pays no
-   stream / staging set-up.  The context must be loaded again before use. */
+   stream / staging set-up.  The context must be loaded again before use: after it
+   every call that needs loaded bytes, ids, a split, a text batch, spans or unpacked
+   rows returns BPE_GPU_ESTATE, as on a new context, bpe_gpu_fetch_merges and
+   bpe_gpu_fetch_merge_log report no entry, and the decoders and
+   bpe_gpu_unpack_rows, which take their input from the caller, work as ever. */
 int bpe_gpu_trim(bpe_gpu_ctx *ctx);
 
 /* number of visible GPUs */
@@ -200,10 +204,15 @@ int bpe_gpu_train(bpe_gpu_ctx *ctx, long max_merges, size_t *n_merges);
 enum { BPE_GPU_FAST = 1 };
 int bpe_gpu_train_ex(bpe_gpu_ctx *ctx, long max_merges, unsigned flags, size_t *n_merges);
 
-/* merges as (a, b) pairs, ids 256.. in order; cap in pairs */
+/* merges of the last bpe_gpu_train / _train_ex as (a, b) pairs, ids 256.. in order; cap in pairs.
+   They live in the run buffers of that training: bpe_gpu_load / _load_fd / _load_texts / _synth / _trim,
+   bpe_gpu_encode / _encode_docs / _encode_split and the next training give those buffers back, and from
+   then on *count is 0 (never an error; the same holds for bpe_gpu_fetch_merge_log).  bpe_gpu_split*,
+   bpe_gpu_train_split, bpe_gpu_map_ids, the decoders, the span, packing and row calls leave them. */
 int bpe_gpu_fetch_merges(bpe_gpu_ctx *ctx, uint32_t *pairs, size_t cap, size_t *count);
 
-/* final token ids of the loaded corpus (after train or encode) */
+/* final token ids of the loaded corpus (after train or encode).  The ids go with the bytes (any load, synth,
+   trim) and are replaced by the next training or encode of any kind; nothing else touches them. */
 int bpe_gpu_fetch_ids(bpe_gpu_ctx *ctx, uint32_t *ids, size_t cap, size_t *len);
 /* ids [first, first + count) of them */
 int bpe_gpu_fetch_ids_range(bpe_gpu_ctx *ctx, size_t first, uint32_t *ids, size_t count);
@@ -231,7 +240,9 @@ int bpe_gpu_decode(bpe_gpu_ctx *ctx, const uint32_t *ids, size_t len,
    bpe_gpu_fetch_ids / _fetch_ids_range / _ids_checksum serve the concatenated ids. */
 int bpe_gpu_encode_docs(bpe_gpu_ctx *ctx, const uint64_t *doc_off, size_t ndocs,
                         const uint32_t *pairs, size_t n_merges);
-/* id_off[0..ndocs] of the last bpe_gpu_encode_docs; out may be NULL, *count = ndocs + 1 */
+/* id_off[0..ndocs] of the last bpe_gpu_encode_docs; out may be NULL, *count = ndocs + 1.  They belong to the ids:
+   a bpe_gpu_encode or a training afterwards leaves ids without documents, and this call, bpe_gpu_docs_info and
+   bpe_gpu_token_spans then return BPE_GPU_ESTATE. */
 int bpe_gpu_fetch_doc_offsets(bpe_gpu_ctx *ctx, uint64_t *out, size_t cap, size_t *count);
 /* out8 = {ndocs, docs through the fallback, windows, windows failed, core, halo, 0, 0} */
 int bpe_gpu_docs_info(bpe_gpu_ctx *ctx, uint64_t *out8);
@@ -411,7 +422,10 @@ int bpe_gpu_docs_window(const uint64_t *doc_off, size_t ndocs, uint64_t n,
  * on the context drop them; bpe_gpu_encode, _encode_docs, _encode_split and
  * _decode keep them (several merge lists may be encoded over one split); a new
  * bpe_gpu_split replaces them.  A call that needs them and finds none returns
- * BPE_GPU_ESTATE.
+ * BPE_GPU_ESTATE.  A split reads the bytes alone: the resident ids of an earlier
+ * encode or training, their document and text offsets, their spans and a
+ * vocabulary mark stay as they were and keep describing the split they were
+ * made over.  A refused call (BPE_GPU_ESTATE) changes nothing on the context.
  * ---------------------------------------------------------------------- */
 enum { BPE_SPLIT_LINES = 0, BPE_SPLIT_WORDS = 1, BPE_SPLIT_GPT2 = 2, BPE_SPLIT_GPT2_UNICODE = 4, BPE_SPLIT_CL100K = 6, BPE_SPLIT_O200K = 8 }; /* (3, 5 and 7 are no presets) */
 /* bytes one workgroup of the split kernels handles per step, and the largest grid

@@ -523,6 +523,7 @@ void free_train(bpe_gpu_ctx *c, bool release = false) {
     for (hipGraphExec_t g : c->retired)
         if (real_graph(g)) (void)hipGraphExecDestroy(g);
     c->retired.clear();
+    c->merges_done = 0;  // h.merges (and h.mlog) are among the buffers released: bpe_gpu_fetch_merges must not read them
     c->spans_ready = false;
     c->ids_ready = false;
     c->ids_mapped = false;
