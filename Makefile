@@ -51,7 +51,11 @@ COBJ_STREAM := $(patsubst $(PKG)/src/%.c,$(BUILD)/%.o,$(CSRC_STREAM))
 # engine call, so tests/asan_rows needs no model)
 CSRC_ROWS := $(PKG)/src/bpe_rows.c
 COBJ_ROWS := $(patsubst $(PKG)/src/%.c,$(BUILD)/%.o,$(CSRC_ROWS))
-HIPDEPS := $(wildcard $(PKG)/csrc/*.hip $(PKG)/csrc/*.h) $(PKG)/src/bpe_split_presets.h $(PKG)/src/bpe_o200k_rule.h include/bpe_gpu.h
+# normalization: src/bpe_normalize.c is host code alone (BPE_NORM_NFC in plain C over src/bpe_nfc_rule.h and
+# csrc/unicode_nfc.h; no engine call)
+CSRC_NORM := $(PKG)/src/bpe_normalize.c
+COBJ_NORM := $(patsubst $(PKG)/src/%.c,$(BUILD)/%.o,$(CSRC_NORM))
+HIPDEPS := $(wildcard $(PKG)/csrc/*.hip $(PKG)/csrc/*.h) $(PKG)/src/bpe_split_presets.h $(PKG)/src/bpe_o200k_rule.h $(PKG)/src/bpe_nfc_rule.h include/bpe_gpu.h
 
 all: $(PKG)/libbpe_amd.so tools/bpe_main oracle
 
@@ -61,10 +65,10 @@ $(BUILD):
 $(BUILD)/engine.o: $(HIPDEPS) | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $(PKG)/csrc/engine.hip -o $@
 
-$(BUILD)/%.o: $(PKG)/src/%.c $(wildcard include/*.h $(PKG)/src/*.h $(PKG)/csrc/unicode_classes.h $(PKG)/csrc/unicode_case_classes.h) | $(BUILD)
+$(BUILD)/%.o: $(PKG)/src/%.c $(wildcard include/*.h $(PKG)/src/*.h $(PKG)/csrc/unicode_classes.h $(PKG)/csrc/unicode_case_classes.h $(PKG)/csrc/unicode_nfc.h) | $(BUILD)
 	$(CC) $(CFLAGS) -c $< -o $@
 
-$(PKG)/libbpe_amd.so: $(BUILD)/engine.o $(COBJ) $(COBJ_GPU) $(COBJ_TS) $(COBJ_SP) $(COBJ_SPECIAL) $(COBJ_VOCAB) $(COBJ_TEXTS) $(COBJ_SPANS) $(COBJ_STREAM) $(COBJ_ROWS)
+$(PKG)/libbpe_amd.so: $(BUILD)/engine.o $(COBJ) $(COBJ_GPU) $(COBJ_TS) $(COBJ_SP) $(COBJ_SPECIAL) $(COBJ_VOCAB) $(COBJ_TEXTS) $(COBJ_SPANS) $(COBJ_STREAM) $(COBJ_ROWS) $(COBJ_NORM)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -lm -ldl -lpthread
 
 tools/bpe_main: tools/bpe_main.c $(PKG)/libbpe_amd.so

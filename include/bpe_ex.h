@@ -93,6 +93,14 @@ int bpe_unicode_info(const char **source, uint64_t *digest);
 int bpe_unicode_case_class(uint32_t cp);
 int bpe_unicode_case_info(const char **source, uint64_t *digest);
 
+/* BPE_NORM_NFC (bpe_gpu.h, "Normalization") in plain C, no GPU: the definition the device is held to
+ * (src/bpe_normalize.c).  Two-phase: *out_len = the length of the normalized text, of which the pieces that fit
+ * into out[cap] are written (out may be NULL with cap 0).  Returns 0, -1 for a bad argument, -3 without memory.
+ * bpe_nfc_info: as bpe_unicode_info, for the tables of csrc/unicode_nfc.h ("unicodedata <unidata_version>", the
+ * FNV-1a 64 of records, decompositions and pairs). */
+int bpe_nfc_host(const uint8_t *bytes, size_t n, uint8_t *out, size_t cap, size_t *out_len);
+int bpe_nfc_info(const char **source, uint64_t *digest);
+
 /* bpe_encode_split with a preset in place of the tables (bpe_gpu_split_preset): the way to
  * BPE_SPLIT_GPT2, which no two tables express.  Results and ownership as bpe_encode_split. */
 uint32_t *bpe_encode_split_preset(const uint8_t *bytes, size_t n, int preset, dyn_arr_t *pair_arr, int device,

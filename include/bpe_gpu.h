@@ -846,6 +846,48 @@ int bpe_gpu_decode_rows(bpe_gpu_ctx *ctx, const uint32_t *pairs, size_t n_merges
    grid takes in one step (more rows: a wave goes on to further rows)} (pure function, no GPU; for the tests) */
 int bpe_gpu_rows_info(uint64_t *out4);
 
+/* ------------------------------------------------------------------------
+ * Normalization: the resident bytes replaced by a Unicode normalization form of
+ * themselves, before they are split.  BPE_NORM_NFC is the one form offered (the
+ * one normalizer byte-level BPE models ship: "normalizer": {"type": "NFC"}).
+ *
+ * The contract.  As a function of the bytes:
+ *   Decoding.  The text is decoded as BPE_SPLIT_GPT2_UNICODE decodes it
+ *     (well-formed UTF-8 per Unicode Table 3-7).  Every byte in no well-formed
+ *     sequence is a character of its own: it passes through unchanged, has ccc 0
+ *     and composes with nothing, as under Python's errors="surrogateescape".
+ *   Result.  The characters are put into NFC (UAX #15): full canonical
+ *     decomposition, canonical ordering by ccc (stable), canonical composition
+ *     with the composition exclusions and algorithmic Hangul, and UTF-8 again.
+ *     The tables are csrc/unicode_nfc.h (bpe_ex.h bpe_nfc_info names their
+ *     source); bpe_ex.h bpe_nfc_host is this contract in plain C.
+ *   Length.  The result may be longer than the input (U+0958 is 3 bytes in and
+ *     6 out) or shorter.  The new length is what every later call sees;
+ *     BPE_GPU_ERANGE, the context unchanged, if it passes 2^32 - 2.
+ *   Text batches.  U+0000 is an inert starter, so every text normalizes on its
+ *     own and the gap bytes survive: nothing composes or reorders across a gap,
+ *     an empty text stays empty.  The texts' byte offsets on the device are
+ *     rewritten, on the device, to the new positions of the gaps.
+ *   State.  Allowed on plain resident bytes only: after bpe_gpu_load, _load_fd,
+ *     _synth or _load_texts and before any split, encode or training of that
+ *     load (BPE_GPU_ESTATE while the context holds a split's offsets or ids).
+ *     BPE_GPU_EINVAL for another form.  A second call is legal and changes
+ *     nothing.  A context that never calls it launches what it always launched.
+ * ---------------------------------------------------------------------- */
+#define BPE_NORM_NFC 1
+/* normalize the resident bytes; *n_out (may be NULL) = their new length */
+int bpe_gpu_normalize(bpe_gpu_ctx *ctx, int form, size_t *n_out);
+/* out4 = {bytes a lane of the normalizing kernels takes, bytes per wave tile, bytes the largest grid takes in one
+   step, entries (decomposed code points) of a segment a lane normalizes itself: a longer one goes to the
+   fallback} (pure function, no GPU; for the tests).  A workgroup takes BPE_GPU_SPLIT_TILE bytes per step. */
+int bpe_gpu_normalize_info(uint64_t *out4);
+/* The resident bytes (of a text batch: with its gap bytes), at most cap of them into out; *len = their number.
+   out may be NULL.  BPE_GPU_ESTATE before a load. */
+int bpe_gpu_fetch_bytes(bpe_gpu_ctx *ctx, uint8_t *out, size_t cap, size_t *len);
+/* The byte offsets of a text batch's texts in the plain join, as loaded or as the last bpe_gpu_normalize left
+   them; out may be NULL, *count = T + 1.  BPE_GPU_ESTATE without a text batch. */
+int bpe_gpu_fetch_text_byte_offsets(bpe_gpu_ctx *ctx, uint64_t *out, size_t cap, size_t *count);
+
 int bpe_gpu_get_stats(bpe_gpu_ctx *ctx, bpe_gpu_stats *st);
 
 /* Position-keyed checksum of the ids of the last train / encode, computed in

@@ -64,6 +64,9 @@ EXPORTS = [
     # bpe_gpu.h / bpe_ex.h: rows back to texts
     "bpe_gpu_unpack_rows", "bpe_gpu_fetch_rows", "bpe_gpu_decode_rows", "bpe_gpu_rows_info", "bpe_rows_check",
     "bpe_unpack_rows_host",
+    # bpe_gpu.h / bpe_ex.h: normalization
+    "bpe_gpu_normalize", "bpe_gpu_normalize_info", "bpe_gpu_fetch_bytes", "bpe_gpu_fetch_text_byte_offsets",
+    "bpe_nfc_host", "bpe_nfc_info",
 ]
 
 
@@ -313,6 +316,12 @@ def load():
     L.bpe_rows_check.argtypes = [rwp, ctypes.c_char_p, sz]
     L.bpe_unpack_rows_host.argtypes = [vp, ctypes.c_int, sz, ctypes.c_uint32, sz, vp, rwp, vp, sz, ctypes.POINTER(sz), vp, vp,
                                        ctypes.c_char_p, sz]
+    L.bpe_gpu_normalize.argtypes = [vp, ctypes.c_int, ctypes.POINTER(sz)]
+    L.bpe_gpu_normalize_info.argtypes = [vp]
+    L.bpe_gpu_fetch_bytes.argtypes = [vp, vp, sz, ctypes.POINTER(sz)]
+    L.bpe_gpu_fetch_text_byte_offsets.argtypes = [vp, vp, sz, ctypes.POINTER(sz)]
+    L.bpe_nfc_host.argtypes = [vp, sz, vp, sz, ctypes.POINTER(sz)]
+    L.bpe_nfc_info.argtypes = [ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_uint64)]
     L.bpe_release_engines.argtypes = []
     L.bpe_release_engines.restype = None
     _LIB = L

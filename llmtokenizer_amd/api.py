@@ -304,6 +304,41 @@ def split_host(data: bytes, rule, specials=None):
     return out
 
 
+NORM_FORMS = {"nfc": 1}  # bpe_gpu.h BPE_NORM_NFC
+
+
+def nfc_host(data: bytes):
+    """The NFC form of `data` (bytes), computed on the host in plain C (bpe_ex.h bpe_nfc_host): the definition
+    Engine.normalize("nfc") is held to.  A byte in no well-formed UTF-8 sequence passes through, as under
+    errors="surrogateescape".  No GPU."""
+    L = _lib.load()
+    buf = np.frombuffer(data, dtype=np.uint8)
+    vp = ctypes.c_void_p
+    n = ctypes.c_size_t(0)
+    _lib.check(L.bpe_nfc_host(buf.ctypes.data_as(vp), buf.size, None, 0, ctypes.byref(n)), "nfc_host")
+    out = np.zeros(max(n.value, 1), dtype=np.uint8)
+    _lib.check(L.bpe_nfc_host(buf.ctypes.data_as(vp), buf.size, out.ctypes.data_as(vp), n.value, ctypes.byref(n)), "nfc_host")
+    return out[:n.value].tobytes()
+
+
+def nfc_info():
+    """{"source", "digest"}: where the committed NFC tables came from ("unicodedata <unidata_version>") and their
+    FNV-1a 64 (bpe_ex.h bpe_nfc_info).  No GPU."""
+    src, dig = ctypes.c_char_p(), ctypes.c_uint64(0)
+    _lib.check(_lib.load().bpe_nfc_info(ctypes.byref(src), ctypes.byref(dig)), "nfc_info")
+    return {"source": src.value.decode(), "digest": int(dig.value)}
+
+
+def normalize_info():
+    """{"thread", "wave", "workgroup", "grid_bytes", "lane_bound"}: bytes a lane of the normalizing kernels takes,
+    bytes per wave tile, per workgroup step (the split kernels' tile) and per grid step, and the entries of a
+    segment a lane normalizes itself (bpe_gpu_normalize_info; for the tests)"""
+    out = np.zeros(4, dtype=np.uint64)
+    _lib.check(_lib.load().bpe_gpu_normalize_info(out.ctypes.data_as(ctypes.c_void_p)), "normalize_info")
+    return {"thread": int(out[0]), "wave": int(out[1]), "workgroup": split_info()["tile"], "grid_bytes": int(out[2]),
+            "lane_bound": int(out[3])}
+
+
 def split_info():
     """{"tile", "grid_bytes"}: bytes one workgroup of the split kernels handles per
     step and bytes one grid step covers (bpe_gpu_split_info; for the tests)"""
@@ -785,6 +820,35 @@ class Engine:
         _lib.check(self.L.bpe_gpu_load_texts(self.ctx, buf.ctypes.data_as(vp), buf.size, off.ctypes.data_as(vp),
                                              off.size - 1), "load_texts")
         return off.size - 1
+
+    def normalize(self, form="nfc"):
+        """replace the resident bytes by their normalization form "nfc" on the device (bpe_gpu_normalize): right
+        after load() or load_texts(), before any split, encode or training.  In a text batch every text
+        normalizes on its own.  Returns the new length of the resident bytes."""
+        if form not in NORM_FORMS and not isinstance(form, int):
+            raise BpeError(f"normalize: form {form!r} (have {sorted(NORM_FORMS)})")
+        n = ctypes.c_size_t(0)
+        _lib.check(self.L.bpe_gpu_normalize(self.ctx, NORM_FORMS.get(form, form), ctypes.byref(n)), "normalize")
+        return n.value
+
+    def bytes(self):
+        """the resident bytes (bpe_gpu_fetch_bytes); of a text batch: every text followed by its gap byte 0x00"""
+        n = ctypes.c_size_t(0)
+        _lib.check(self.L.bpe_gpu_fetch_bytes(self.ctx, None, 0, ctypes.byref(n)), "fetch_bytes")
+        out = np.zeros(max(n.value, 1), dtype=np.uint8)
+        _lib.check(self.L.bpe_gpu_fetch_bytes(self.ctx, out.ctypes.data_as(ctypes.c_void_p), n.value, ctypes.byref(n)),
+                   "fetch_bytes")
+        return out[:n.value].tobytes()
+
+    def text_byte_offsets(self):
+        """byte offsets of a text batch's texts in the plain join (uint64, texts + 1 entries), as loaded or as
+        normalize() left them (bpe_gpu_fetch_text_byte_offsets)"""
+        n = ctypes.c_size_t(0)
+        _lib.check(self.L.bpe_gpu_fetch_text_byte_offsets(self.ctx, None, 0, ctypes.byref(n)), "fetch_text_byte_offsets")
+        out = np.zeros(n.value, dtype=np.uint64)
+        _lib.check(self.L.bpe_gpu_fetch_text_byte_offsets(self.ctx, out.ctypes.data_as(ctypes.c_void_p), n.value,
+                                                          ctypes.byref(n)), "fetch_text_byte_offsets")
+        return out
 
     def text_offsets(self):
         """id offsets of the texts after encode_split() over a text batch (uint64, texts + 1 entries:

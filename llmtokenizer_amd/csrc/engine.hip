@@ -36,6 +36,7 @@
 #include "spans.hip"
 #include "stream.hip"
 #include "rows.hip"
+#include "normalize.hip"
 
 // (bpe_ex.h, src/bpe_texts.c: the host definition of a text batch's offsets and its resident bytes)
 extern "C" int bpe_texts_check(const uint64_t *text_off, size_t T, size_t n, char *msg, size_t msg_cap);
@@ -396,6 +397,8 @@ struct bpe_gpu_ctx {
     uint32_t *d_skew = nullptr;  // k_pair_skew_sample's {largest pair count, pairs sampled} (device)
     uint32_t skew[3] = {0, 0, 0};   // ... on the host once skew_valid
     bool skew_valid = false;
+    uint8_t *nf_spare = nullptr;  // bpe_gpu_normalize: the buffer the bytes lay in before the last call that moved them
+    size_t nf_spare_cap = 0;      // (kept across loads; bpe_gpu_trim and bpe_gpu_destroy free it)
     uint32_t *d_pres = nullptr;  // [256] byte presence gathered while bpe_gpu_load_fd streamed the corpus
     bool pres_valid = false;     // d_pres describes the bytes loaded now
 };
@@ -2620,6 +2623,7 @@ void bpe_gpu_destroy(bpe_gpu_ctx *c) {
     for (auto &e : c->ev_probe)
         if (e) (void)hipEventDestroy(e);
     if (c->d_pres) hipFree(c->d_pres);
+    if (c->nf_spare) hipFree(c->nf_spare);
     if (c->d_enc_pairs) hipFree(c->d_enc_pairs);
     if (c->d_split) hipFree(c->d_split);
     if (c->d_sp_pieces) hipFree(c->d_sp_pieces);
@@ -2651,6 +2655,11 @@ static int alloc_bytes(bpe_gpu_ctx *c, size_t n) {
     c->split_ready = false;  // the split's offsets describe the bytes replaced here
     c->tx_on = false;        // ... and so do a text batch's breaks
     c->tx_T = 0;
+    if (c->nf_spare && c->nf_spare_cap < n + 64) {  // (bpe_gpu_normalize's second buffer: kept while it fits the corpus)
+        (void)hipFree(c->nf_spare);
+        c->nf_spare = nullptr;
+        c->nf_spare_cap = 0;
+    }
     if (!c->h.bytes || c->bytes_cap < n + 64) {  // (a buffer at least this large is kept)
         if (c->h.bytes) { (void)hipFree(c->h.bytes); c->h.bytes = nullptr; }
         HIPCHK(hipMalloc(&c->h.bytes, n + 64));
@@ -3414,6 +3423,9 @@ int bpe_gpu_trim(bpe_gpu_ctx *c) {
     }
     if (c->d_enc_pairs) (void)hipFree(c->d_enc_pairs);
     c->d_enc_pairs = nullptr;
+    if (c->nf_spare) (void)hipFree(c->nf_spare);
+    c->nf_spare = nullptr;
+    c->nf_spare_cap = 0;
     return 0;
 }
 
@@ -4213,6 +4225,161 @@ int bpe_gpu_decode_rows(bpe_gpu_ctx *c, const uint32_t *pairs, size_t n_merges, 
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(byte_off, d_out, (B + 1) * 8, hipMemcpyDeviceToHost, c->st));
     HIPCHK(hipStreamSynchronize(c->st));
+    return 0;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------ normalization (normalize.hip; the definition: src/bpe_normalize.c)
+
+extern "C" {
+
+int bpe_gpu_normalize_info(uint64_t *out4) {
+    if (!out4) return BPE_GPU_EINVAL;
+    out4[0] = NF_PER;
+    out4[1] = NF_WAVE;
+    out4[2] = (uint64_t)NF_TILE * NF_GRID;
+    out4[3] = NF_LANE;
+    return 0;
+}
+
+int bpe_gpu_fetch_bytes(bpe_gpu_ctx *c, uint8_t *out, size_t cap, size_t *len) {
+    if (!c || !len) return BPE_GPU_EINVAL;
+    if (!c->loaded) return fail(BPE_GPU_ESTATE, "fetch_bytes before load");
+    HIPCHK(hipSetDevice(c->dev));
+    *len = (size_t)c->n0;
+    const size_t n = std::min<size_t>(cap, (size_t)c->n0);
+    if (n && out) return d2h_staged(c, out, c->h.bytes, n);
+    return 0;
+}
+
+int bpe_gpu_fetch_text_byte_offsets(bpe_gpu_ctx *c, uint64_t *out, size_t cap, size_t *count) {
+    if (!c || !count) return BPE_GPU_EINVAL;
+    if (!c->tx_on) return fail(BPE_GPU_ESTATE, "no text byte offsets: the context holds no text batch (bpe_gpu_load_texts)");
+    HIPCHK(hipSetDevice(c->dev));
+    *count = (size_t)c->tx_T + 1;
+    const size_t k = std::min<size_t>(cap, *count);
+    if (k && out) {
+        HIPCHK(hipMemcpyAsync(out, c->dscr[DS_TX_BOFF], k * 8, hipMemcpyDeviceToHost, c->st));
+        HIPCHK(hipStreamSynchronize(c->st));
+    }
+    return 0;
+}
+
+int bpe_gpu_normalize(bpe_gpu_ctx *c, int form, size_t *n_out) {
+    if (!c) return BPE_GPU_EINVAL;
+    if (form != BPE_NORM_NFC) return fail(BPE_GPU_EINVAL, "normalize: unknown form (BPE_NORM_NFC is the one offered)");
+    if (!c->loaded) return fail(BPE_GPU_ESTATE, "normalize before load");
+    if (c->split_ready || c->ids_ready || c->ts_ready)
+        return fail(BPE_GPU_ESTATE, "normalize: the context holds a split or ids of these bytes: normalize right after the load");
+    if (c->sharded) return fail(BPE_GPU_ESTATE, "normalize: the context is a shard of a group: a segment could cross the shard's edge");
+    HIPCHK(hipSetDevice(c->dev));
+    if (n_out) *n_out = (size_t)c->n0;
+    const uint64_t n = c->n0, ntiles = (n + NF_TILE - 1) / NF_TILE;
+    if (!n) return 0;
+    int r;
+    unsigned long long *d_cnt, *d_off, *d_queue;
+    uint32_t *d_ctl;
+    uint32_t qcap = 1u << 12;
+    if ((r = dscratch(c, DS_NF_CNT, (ntiles + 1) * 8, &d_cnt)) || (r = dscratch(c, DS_NF_OFF, (ntiles + 1) * 8, &d_off)) ||
+        (r = dscratch(c, DS_NF_CTL, NFC_WORDS * 4, &d_ctl)))
+        return r;
+    NfArgs A{};
+    A.b = c->h.bytes;
+    A.n = n;
+    A.ctl = d_ctl;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(ntiles, NF_GRID);
+    uint32_t ctl[NFC_WORDS];
+    for (int turn = 0;; turn++) {  // (a second turn when the queue was too short for the first)
+        if ((r = dscratch(c, DS_NF_QUEUE, (size_t)qcap * 8, &d_queue))) return r;
+        A.queue = d_queue;
+        A.qcap = qcap;
+        HIPCHK(hipMemsetAsync(d_ctl, 0, NFC_WORDS * 4, c->st));
+        HIPCHK(hipMemsetAsync(d_cnt + ntiles, 0, 8, c->st));
+        k_nf_measure<<<grid, NF_T, 0, c->st>>>(A, d_cnt);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(ctl, d_ctl, sizeof ctl, hipMemcpyDeviceToHost, c->st));
+        HIPCHK(hipStreamSynchronize(c->st));
+        if (ctl[NFC_QCOUNT] <= qcap) break;
+        if (turn) return fail(BPE_GPU_EINTERNAL, "normalize: the queue of long segments grew between two passes");
+        qcap = ctl[NFC_QCOUNT];
+    }
+    if (!ctl[NFC_DIRTY]) return 0;  // no dirty segment: the bytes are in NFC as they lie
+    const uint32_t nq = ctl[NFC_QCOUNT];
+    NfLong *d_ent = nullptr;
+    uint32_t *d_ws = nullptr;
+    if (nq) {
+        if ((r = dscratch(c, DS_NF_ENT, (size_t)nq * sizeof(NfLong), &d_ent))) return r;
+        k_nf_long_len<<<(nq + 63) / 64, 64, 0, c->st>>>(A, d_ent, nq);
+        HIPCHK(hipGetLastError());
+        std::vector<NfLong> ent(nq);
+        HIPCHK(hipMemcpyAsync(ent.data(), d_ent, (size_t)nq * sizeof(NfLong), hipMemcpyDeviceToHost, c->st));
+        HIPCHK(hipStreamSynchronize(c->st));
+        std::sort(ent.begin(), ent.end(), [](const NfLong &x, const NfLong &y) { return x.start < y.start; });
+        unsigned long long words = 0;
+        for (NfLong &e : ent) {
+            e.ws = words;
+            words += 2 * e.ncp;
+        }
+        if ((r = dscratch(c, DS_NF_WS, (size_t)std::max<unsigned long long>(words, 1) * 4, &d_ws))) return r;
+        HIPCHK(hipMemcpyAsync(d_ent, ent.data(), (size_t)nq * sizeof(NfLong), hipMemcpyHostToDevice, c->st));
+        HIPCHK(hipStreamSynchronize(c->st));  // (`ent` goes at the end of this block)
+        k_nf_long_run<<<nq, 64, 0, c->st>>>(A, d_ent, d_ws, d_cnt);
+        HIPCHK(hipGetLastError());
+    }
+    A.ent = d_ent;
+    A.nent = nq;
+    if ((r = ROCPRIM_RUN(c, DS_NF_TMP, rocprim::exclusive_scan(tmp, tb, d_cnt, d_off, 0ull, (size_t)ntiles + 1, rocprim::plus<unsigned long long>(), c->st))))
+        return r;
+    unsigned long long total = 0;
+    HIPCHK(hipMemcpyAsync(&total, d_off + ntiles, 8, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipStreamSynchronize(c->st));
+    if (total > 0xFFFFFFFEull) return fail(BPE_GPU_ERANGE, "normalize: the normalized text is larger than 2^32-2 bytes");
+    uint64_t *d_boff = nullptr;
+    if (c->tx_on) {
+        if ((r = dscratch(c, DS_NF_BOFF, (size_t)(c->tx_T + 1) * 8, &d_boff))) return r;
+        A.boff = (const uint64_t *)c->dscr[DS_TX_BOFF];
+        A.boff_new = d_boff;
+        A.T = c->tx_T;
+    }
+    // the destination: the buffer the last normalize left (nf_spare) when it is large enough, else a new one
+    uint8_t *d_new = c->nf_spare;
+    size_t new_cap = c->nf_spare_cap;
+    c->nf_spare = nullptr;
+    c->nf_spare_cap = 0;
+    if (!d_new || new_cap < (size_t)total + 64) {
+        if (d_new) (void)hipFree(d_new);
+        d_new = nullptr;
+        new_cap = (size_t)total + 64;
+        if (hipMalloc(&d_new, new_cap) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(BPE_GPU_ENOMEM, "normalize: no memory for the normalized bytes");
+        }
+    }
+    hipError_t e = hipMemsetAsync(d_new + total, 0, 64, c->st);
+    if (e == hipSuccess) {
+        k_nf_write<<<grid, NF_T, 0, c->st>>>(A, d_off, d_new, total);
+        if (nq) k_nf_long_write<<<nq, 64, 0, c->st>>>(d_ent, d_ws, d_new, total);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(ctl, d_ctl, sizeof ctl, hipMemcpyDeviceToHost, c->st);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->st);
+    if (e != hipSuccess || ctl[NFC_ERR]) {
+        (void)hipFree(d_new);
+        return e != hipSuccess ? fail(BPE_GPU_EHIP, "normalize: the write pass", e)
+                               : fail(BPE_GPU_EINTERNAL, "normalize: a long segment of pass 2 was not queued by pass 1");
+    }
+    // (only now, with nothing refused: the context is as it was after every return above)
+    if (c->tx_on) HIPCHK(hipMemcpyAsync(c->dscr[DS_TX_BOFF], d_boff, (size_t)(c->tx_T + 1) * 8, hipMemcpyDeviceToDevice, c->st));
+    c->nf_spare = c->h.bytes;  // the old bytes' buffer is the next call's destination: no hipMalloc / hipFree per call
+    c->nf_spare_cap = c->bytes_cap;
+    c->h.bytes = d_new;
+    c->bytes_cap = new_cap;
+    c->n0 = total;
+    c->skew_valid = false;
+    if ((r = ingest_presence(c, (size_t)total))) return r;
+    HIPCHK(hipStreamSynchronize(c->st));
+    if (n_out) *n_out = (size_t)total;
     return 0;
 }
 

@@ -690,6 +690,14 @@ enum DScr {
     DS_ROWS_TMP,         // bpe_gpu_unpack_rows: rocprim temporary of that scan
     DS_ROWS_IDS,         // bpe_gpu_unpack_rows: the kept ids; stays until the next unpack (bpe_gpu_decode_rows copies them)
     DS_ROWS_ERR,         // bpe_gpu_unpack_rows: the two error words
+    DS_NF_CNT,           // bpe_gpu_normalize: the worth of every tile in output bytes [tiles + 1]
+    DS_NF_OFF,           // ... and their scan, the tiles' output offsets
+    DS_NF_TMP,           // bpe_gpu_normalize: rocprim temporary of that scan
+    DS_NF_CTL,           // bpe_gpu_normalize: control words (NFC_*)
+    DS_NF_QUEUE,         // bpe_gpu_normalize: the starts of the segments that outgrow a lane
+    DS_NF_ENT,           // ... what the fallback knows of each (NfLong), sorted by start
+    DS_NF_WS,            // ... and the entries it orders and composes
+    DS_NF_BOFF,          // bpe_gpu_normalize: a text batch's new byte offsets, copied to DS_TX_BOFF at the end
     DS_COUNT
 };
 // bpe_gpu_train_split takes its eight token-sized arrays as one run of slots

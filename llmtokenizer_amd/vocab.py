@@ -30,6 +30,7 @@ O200K_PATTERN = (r"[^\r\n\p{L}\p{N}]?[\p{Lu}\p{Lt}\p{Lm}\p{Lo}\p{M}]*[\p{Ll}\p{L
                  r"|\p{N}{1,3}| ?[^\s\p{L}\p{N}]+[\r\n/]*|\s*[\r\n]+|\s+(?!\S)|\s+")
 SPLIT_PATTERNS = {"cl100k": CL100K_PATTERN, "o200k": O200K_PATTERN}  # the Split patterns a tokenizer.json can name
 RULES = ("gpt2_unicode", "cl100k", "o200k")  # the presets a vocabulary file can name
+NORMALIZERS = {"NFC": "nfc"}  # the normalizer types a tokenizer.json can name and Vocab.normalizer's word for each
 ID_LIMIT = 1 << 24
 
 
@@ -110,15 +111,19 @@ def vocab_tables(vocab):
 
 class Vocab:
     """merges (k, 2) uint32; byte_ids (256), merge_ids (k), special_ids (len(specials)) uint32: the vocabulary
-    id of every byte, merge and special; specials: list of bytes; rule: a preset name of api.SPLIT_PRESETS"""
+    id of every byte, merge and special; specials: list of bytes; rule: a preset name of api.SPLIT_PRESETS;
+    normalizer: None or "nfc" (Engine.normalize runs between the load and the split)"""
 
-    def __init__(self, merges, byte_ids, merge_ids, special_ids, specials, rule):
+    def __init__(self, merges, byte_ids, merge_ids, special_ids, specials, rule, normalizer=None):
         self.merges = np.ascontiguousarray(merges, dtype=np.uint32).reshape(-1, 2)
         self.byte_ids = np.ascontiguousarray(byte_ids, dtype=np.uint32).reshape(-1)
         self.merge_ids = np.ascontiguousarray(merge_ids, dtype=np.uint32).reshape(-1)
         self.special_ids = np.ascontiguousarray(special_ids, dtype=np.uint32).reshape(-1)
         self.specials = [bytes(s) for s in specials]
         self.rule = rule
+        self.normalizer = normalizer
+        if normalizer is not None and normalizer not in api.NORM_FORMS:
+            raise BpeError(f"vocabulary: normalizer {normalizer!r} (None or one of {sorted(api.NORM_FORMS)})")
         if rule not in api.SPLIT_PRESETS:
             raise BpeError(f"vocabulary: no preset {rule!r} (have {sorted(api.SPLIT_PRESETS)})")
         if self.byte_ids.size != 256 or self.special_ids.size != len(self.specials):
@@ -127,12 +132,14 @@ class Vocab:
         self.check()
 
     def __eq__(self, other):
-        return (isinstance(other, Vocab) and self.rule == other.rule and self.specials == other.specials and
+        return (isinstance(other, Vocab) and self.rule == other.rule and self.normalizer == other.normalizer and
+                self.specials == other.specials and
                 all(np.array_equal(getattr(self, k), getattr(other, k))
                     for k in ("merges", "byte_ids", "merge_ids", "special_ids")))
 
     def __repr__(self):
-        return f"Vocab(rule={self.rule!r}, merges={self.merges.shape[0]}, specials={len(self.specials)})"
+        norm = f", normalizer={self.normalizer!r}" if self.normalizer else ""
+        return f"Vocab(rule={self.rule!r}, merges={self.merges.shape[0]}, specials={len(self.specials)}{norm})"
 
     def c_vocab(self):
         if self._c is None:
@@ -174,7 +181,7 @@ class Vocab:
         return cls(m, np.arange(256), 256 + np.arange(k), 256 + k + np.arange(s), specials, rule)
 
     @classmethod
-    def _assemble(cls, tokens, merges, specials, rule, where):
+    def _assemble(cls, tokens, merges, specials, rule, where, normalizer=None):
         """tokens: {bytes: id} of the model's vocabulary; merges: [(bytes, bytes)] in rank order; specials:
         [(bytes, id)].  Numbers the merges, checks reachability and returns the Vocab."""
         special_ids = {i for _, i in specials}
@@ -212,13 +219,16 @@ class Vocab:
             raise BpeError(f"{where}: {len(bad)} token(s) cannot be reached by the merges from their bytes: {first}"
                            f"{', ...' if len(bad) > 5 else ''}")
         return cls(np.array(pairs, dtype=np.uint32).reshape(-1, 2), byte_ids, merge_ids, [i for _, i in specials],
-                   [s for s, _ in specials], rule)
+                   [s for s, _ in specials], rule, normalizer)
 
     @classmethod
-    def from_tokenizer_json(cls, path):
+    def from_tokenizer_json(cls, path, normalizers=()):
         """read a byte-level BPE tokenizer.json.  The rule comes from its pre-tokenizer (ByteLevel with
         use_regex: "gpt2_unicode"; Sequence[Split(the cl100k or the o200k pattern, Isolated), ByteLevel(use_regex
-        false)]: "cl100k" or "o200k"), the specials from added_tokens.  Refused, by name: add_prefix_space, a normalizer,
+        false)]: "cl100k" or "o200k"), the specials from added_tokens.  normalizers: the normalizer types the caller
+        accepts; with ("NFC",) a file whose normalizer is exactly {"type": "NFC"} loads with normalizer="nfc" (Qwen2's
+        files carry it), and the text is then normalized on the device before the split.  Refused, by name:
+        add_prefix_space, a normalizer the caller did not name or that is no plain NFC,
         byte_fallback, dropout, a subword prefix or suffix, an added token with lstrip / rstrip / single_word /
         normalized, any other pre-tokenizer or pattern, a model type other than BPE, and a vocabulary with a
         token its merges do not reach.  A post-processor (Llama 3's adds <|begin_of_text|>) is not applied:
@@ -230,8 +240,17 @@ class Vocab:
         model = j.get("model") or {}
         if model.get("type", "BPE") != "BPE":
             raise BpeError(f"{where}: model type {model.get('type')!r}, only BPE is read")
+        normalizer = None
         if j.get("normalizer") is not None:
-            raise BpeError(f"{where}: a normalizer ({j['normalizer'].get('type')!r}) is not supported")
+            kind = j["normalizer"].get("type") if isinstance(j["normalizer"], dict) else None
+            if not isinstance(kind, str) or kind not in NORMALIZERS or j["normalizer"] != {"type": kind}:
+                kind = kind if isinstance(kind, str) else type(j["normalizer"]).__name__
+                raise BpeError(f"{where}: a normalizer ({kind!r}) is not supported (only a plain "
+                               f"{' / '.join(NORMALIZERS)} is, with normalizers=)")
+            if kind not in tuple(normalizers):
+                raise BpeError(f"{where}: a normalizer ({kind!r}) is not supported unless it is asked for: "
+                               f"from_tokenizer_json(path, normalizers=({kind!r},))")
+            normalizer = NORMALIZERS[kind]
         if model.get("byte_fallback"):
             raise BpeError(f"{where}: byte_fallback is not supported")
         if model.get("dropout"):
@@ -260,7 +279,7 @@ class Vocab:
             if len(parts) != 2:
                 raise BpeError(f"{where}: merge {r} ({m!r}) is not a pair")
             merges.append(tuple(_from_alphabet(p, f"{where}: merge {r}: part") for p in parts))
-        return cls._assemble(tokens, merges, specials, rule, where)
+        return cls._assemble(tokens, merges, specials, rule, where, normalizer)
 
     @staticmethod
     def _rule_of(pt, where):
@@ -378,7 +397,8 @@ class Vocab:
             vocab[content] = int(i)
             added.append({"id": int(i), "content": content, "single_word": False, "lstrip": False, "rstrip": False,
                           "normalized": False, "special": True})
-        doc = {"version": "1.0", "truncation": None, "padding": None, "added_tokens": added, "normalizer": None,
+        doc = {"version": "1.0", "truncation": None, "padding": None, "added_tokens": added,
+               "normalizer": {"type": next(k for k, w in NORMALIZERS.items() if w == self.normalizer)} if self.normalizer else None,
                "pre_tokenizer": pre, "post_processor": None, "decoder": dict(byte_level, use_regex=True),
                "model": {"type": "BPE", "dropout": None, "unk_token": None, "continuing_subword_prefix": None,
                          "end_of_word_suffix": None, "fuse_unk": False, "byte_fallback": False, "ignore_merges": False,
@@ -413,6 +433,17 @@ class Tokenizer:
             raise BpeError(f"{what}: return_spans {return_spans!r} (None, \"byte\" or \"char\")")
         return return_spans
 
+    def _load(self, what, texts, unit=None, batch=True):
+        """the load of every encode: the texts (or the one text), normalized when the vocabulary asks for it"""
+        e, v = self._eng(), self.vocab
+        if v.normalizer is not None and unit is not None:
+            raise BpeError(f"{what}: return_spans with a normalizing vocabulary (normalizer={v.normalizer!r}) is not "
+                           "offered: the spans would count the normalized text, not the caller's")
+        n = e.load_texts(texts) if batch else e.load(texts)
+        if v.normalizer is not None:
+            e.normalize(v.normalizer)
+        return n
+
     def _spans(self, unit):
         v = self.vocab
         return self._eng().token_spans(v.merges, v.specials or None, vocab=v, unit=unit)
@@ -428,7 +459,7 @@ class Tokenizer:
         if isinstance(data, str):
             data = data.encode("utf-8")
         e, v = self._eng(), self.vocab
-        e.load(data)
+        self._load("encode", data, unit, batch=False)
         e.split(v.rule, v.specials or None)
         e.encode_split(v.merges)
         e.map_ids(v)
@@ -474,7 +505,7 @@ class Tokenizer:
                         raise BpeError(f'encode_batch: return_tensors="pt" with return_spans: text {k} holds 2^31 bytes '
                                        "or more, its spans do not fit int32")
         e, v = self._eng(), self.vocab
-        n_texts = e.load_texts(texts)
+        n_texts = self._load("encode_batch", texts, unit)
         e.split(v.rule, v.specials or None)
         e.encode_split(v.merges)
         e.map_ids(v)
@@ -527,7 +558,7 @@ class Tokenizer:
                 raise BpeError('encode_packed: return_tensors="pt": torch sees no GPU; import torch before the first '
                                "call into llmtokenizer_amd, so that both share one HIP runtime")
         e, v = self._eng(), self.vocab
-        e.load_texts(texts)
+        self._load("encode_packed", texts)
         e.split(v.rule, v.specials or None)
         e.encode_split(v.merges)
         e.map_ids(v)
