@@ -47,6 +47,10 @@ COBJ_SPANS := $(patsubst $(PKG)/src/%.c,$(BUILD)/%.o,$(CSRC_SPANS))
 # call, so tests/asan_stream needs no model)
 CSRC_STREAM := $(PKG)/src/bpe_stream.c
 COBJ_STREAM := $(patsubst $(PKG)/src/%.c,$(BUILD)/%.o,$(CSRC_STREAM))
+# whole-text rows: src/bpe_whole.c is host code alone (the description's check and the placement's and the rows'
+# definition; no engine call)
+CSRC_WHOLE := $(PKG)/src/bpe_whole.c
+COBJ_WHOLE := $(patsubst $(PKG)/src/%.c,$(BUILD)/%.o,$(CSRC_WHOLE))
 # rows back to texts: src/bpe_rows.c is host code alone (the description's check and the unpack's definition; no
 # engine call, so tests/asan_rows needs no model)
 CSRC_ROWS := $(PKG)/src/bpe_rows.c
@@ -68,7 +72,7 @@ $(BUILD)/engine.o: $(HIPDEPS) | $(BUILD)
 $(BUILD)/%.o: $(PKG)/src/%.c $(wildcard include/*.h $(PKG)/src/*.h $(PKG)/csrc/unicode_classes.h $(PKG)/csrc/unicode_case_classes.h $(PKG)/csrc/unicode_nfc.h) | $(BUILD)
 	$(CC) $(CFLAGS) -c $< -o $@
 
-$(PKG)/libbpe_amd.so: $(BUILD)/engine.o $(COBJ) $(COBJ_GPU) $(COBJ_TS) $(COBJ_SP) $(COBJ_SPECIAL) $(COBJ_VOCAB) $(COBJ_TEXTS) $(COBJ_SPANS) $(COBJ_STREAM) $(COBJ_ROWS) $(COBJ_NORM)
+$(PKG)/libbpe_amd.so: $(BUILD)/engine.o $(COBJ) $(COBJ_GPU) $(COBJ_TS) $(COBJ_SP) $(COBJ_SPECIAL) $(COBJ_VOCAB) $(COBJ_TEXTS) $(COBJ_SPANS) $(COBJ_STREAM) $(COBJ_WHOLE) $(COBJ_ROWS) $(COBJ_NORM)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -lm -ldl -lpthread
 
 tools/bpe_main: tools/bpe_main.c $(PKG)/libbpe_amd.so

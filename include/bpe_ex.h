@@ -207,6 +207,19 @@ int bpe_pack_stream_host(const uint32_t *ids, size_t n, const uint64_t *text_off
                          uint32_t *rows, uint32_t *seg, uint32_t *pos, size_t rows_cap, size_t *n_rows,
                          uint64_t *n_stream);
 
+/* Whole-text rows (bpe_gpu.h, "Whole-text rows").  bpe_whole_check: 0 for a description bpe_gpu_pack_whole takes;
+ * BPE_GPU_EINVAL for s == NULL, seq_len == 0 or a flag bit that is neither BPE_WHOLE_BOS nor BPE_WHOLE_EOS,
+ * BPE_GPU_ERANGE for seq_len above 2^24; msg (may be NULL) receives a message that names the field.  No GPU. */
+int bpe_whole_check(const bpe_gpu_whole *s, char *msg, size_t msg_cap);
+/* The whole-text rows of ids[0 .. n) held as T texts (text_off as bpe_pack_stream_host takes it): rows[R][seq_len],
+ * seg and pos of the same shape unless NULL, text_row[T] and text_col[T] unless NULL, as bpe_gpu.h defines them.
+ * Plain loops, text by text and cell by cell: this is the definition the device is held to.  *n_rows = R,
+ * *n_cells = n + T w and *n_long (each may be NULL); with rows == NULL nothing else is written.  BPE_GPU_EINVAL for
+ * rows_cap < R and for bad offsets, BPE_GPU_ERANGE for 2^32 rows or more, and what bpe_whole_check refuses.  No GPU. */
+int bpe_pack_whole_host(const uint32_t *ids, size_t n, const uint64_t *text_off, size_t T, const bpe_gpu_whole *s,
+                        uint32_t *rows, uint32_t *seg, uint32_t *pos, uint32_t *text_row, uint32_t *text_col,
+                        size_t rows_cap, size_t *n_rows, uint64_t *n_cells, uint64_t *n_long);
+
 /* Rows back to texts (bpe_gpu.h, "Rows back to texts").  bpe_rows_check: 0 for a description bpe_gpu_unpack_rows
  * takes; BPE_GPU_EINVAL for desc == NULL, a flag bit that is neither BPE_ROWS_PAD nor BPE_ROWS_SKIP, n_stop above 8
  * and, under BPE_ROWS_SKIP, n_skip above 256 or n_skip ids without a skip pointer; msg (may be NULL) receives a

@@ -767,6 +767,72 @@ int bpe_gpu_pack_stream(bpe_gpu_ctx *ctx, const bpe_gpu_stream *s, uint32_t *row
 int bpe_gpu_stream_info(uint64_t *out4);
 
 /* ------------------------------------------------------------------------
+ * Whole-text rows: training rows that never split a text that fits one.
+ *
+ * The contract.  Given the resident ids of a text batch (mapped or not), their
+ * text_off[0 .. T], a row length L (1 <= L <= 2^24), an optional BOS id, an
+ * optional EOS id and a pad id, as in "Packed streams": b = 1 with a BOS, else 0,
+ * e the same for the EOS, w = b + e.  Text k has the cells [bos] if b, its ids,
+ * [eos] if e: w_k = text_off[k + 1] - text_off[k] + w of them.
+ *
+ * The placement (order-preserving next-fit).  A cursor (row, col) starts at
+ * (0, 0); the texts are placed in order:
+ *   w_k == 0 (an empty text, no BOS / EOS): the text occupies nothing, opens no
+ *       row and leaves the cursor where it is;
+ *   0 < w_k <= L: when col + w_k > L the row is closed and the cursor moves to
+ *       (row + 1, 0).  The text takes the w_k cells from the cursor on, and the
+ *       cursor moves behind them; a text that fills the row exactly fits, and the
+ *       cursor then stands at (row + 1, 0);
+ *   w_k > L (a long text, which cannot be kept whole): when col > 0 the row is
+ *       closed first.  The text takes ceil(w_k / L) rows of its own, cut every L
+ *       cells as the stream cuts; no other text joins its last row, the cursor
+ *       moves to column 0 of the row behind it.
+ * text_row[k], text_col[k] = the cursor where text k's first cell went; for a
+ * text with w_k == 0 the cursor as it stood (where the next cell would go: this
+ * may be row R).  R = the rows that hold a cell, 0 when no text has one;
+ * n_cells = n + T w, the occupied cells; n_long = the texts with w_k > L.
+ *
+ * The rows.  Every cell that no text took holds pad_id (any row may end in pad
+ * cells, so there is no drop_last).  For cell c = r L + col of text k, the
+ * o-th of its cells:
+ *   rows[c] = bos_id for b and o == 0, eos_id for e and o == w_k - 1, else the
+ *             text's id o - b;
+ *   seg[c]  = k; BPE_STREAM_NO_TEXT in a pad cell;
+ *   pos[c]  = o for a text's first row, and col in a later row of a long text
+ *             (the stream's rule: from the text's first cell or the row's); 0 in
+ *             a pad cell.
+ *
+ * bpe_gpu_pack_whole computes placement and rows on the device (whole.hip): the
+ * placement is a chain as long as the batch (where a row ends decides where the
+ * next begins), resolved by pointer doubling in ceil(log2(T + 1)) rounds and two
+ * scans, with no loop whose trip count depends on the data.  bpe_ex.h
+ * bpe_pack_whole_host is the same in plain loops.
+ * ---------------------------------------------------------------------- */
+#define BPE_WHOLE_BOS 1u /* flags: bos_id opens every text */
+#define BPE_WHOLE_EOS 2u /* ... eos_id closes every text */
+#define BPE_WHOLE_FLAGS 3u
+typedef struct {
+    uint32_t seq_len, flags, bos_id, eos_id, pad_id;
+} bpe_gpu_whole;
+/* The whole-text rows of the resident text batch: rows[R][seq_len] uint32, seg and pos of the same shape unless
+   NULL, text_row[T] and text_col[T] unless NULL.  rows == NULL is the query: *n_rows = R, *n_cells and *n_long are
+   reported (each may be NULL) and nothing else is written.  Unlike bpe_gpu_pack_stream's, this query runs the
+   placement on the device; the context keeps it, and a following call with the same seq_len and flags fills the
+   rows from it (whatever replaces or drops the batch's ids drops it, as does bpe_gpu_trim).  rows_cap,
+   out_is_device: as bpe_gpu_pack_stream (with out_is_device all five are device pointers).
+   BPE_GPU_EINVAL for seq_len == 0, an unknown flag bit, rows_cap < R, a device pointer that is none of the
+   context's device or not 4-byte aligned; BPE_GPU_ERANGE for seq_len above 2^24 and for 2^32 rows or more (a
+   text_row could not hold them); BPE_GPU_ESTATE without a text batch or without its ids.  The message names the
+   cause, and the context goes on working. */
+int bpe_gpu_pack_whole(bpe_gpu_ctx *ctx, const bpe_gpu_whole *s, uint32_t *rows, uint32_t *seg, uint32_t *pos,
+                       uint32_t *text_row, uint32_t *text_col, int out_is_device, size_t rows_cap, size_t *n_rows,
+                       uint64_t *n_cells, uint64_t *n_long);
+/* out4 = {texts one lane of the placement kernels takes per step, texts per workgroup step, texts the largest grid
+   takes in one step (past that many a lane takes several, a grid step apart), cells one lane of k_fill_whole<true>
+   takes per step (k_fill_whole<false>: one)} (pure function, no GPU; for the tests) */
+int bpe_gpu_whole_info(uint64_t *out4);
+
+/* ------------------------------------------------------------------------
  * Rows back to texts: the ids of a [B, L] grid of cells, as a model hands it
  * back, cut to the text of every row and decoded; the inverse of
  * bpe_gpu_pack_texts.  No id passes through the host.

@@ -61,6 +61,8 @@ EXPORTS = [
     "bpe_token_spans_host",
     # bpe_gpu.h / bpe_ex.h: packed streams
     "bpe_gpu_pack_stream", "bpe_gpu_stream_info", "bpe_stream_check", "bpe_pack_stream_host",
+    # bpe_gpu.h / bpe_ex.h: whole-text rows
+    "bpe_gpu_pack_whole", "bpe_gpu_whole_info", "bpe_whole_check", "bpe_pack_whole_host",
     # bpe_gpu.h / bpe_ex.h: rows back to texts
     "bpe_gpu_unpack_rows", "bpe_gpu_fetch_rows", "bpe_gpu_decode_rows", "bpe_gpu_rows_info", "bpe_rows_check",
     "bpe_unpack_rows_host",
@@ -83,6 +85,11 @@ class VocabIds(ctypes.Structure):
 
 class Stream(ctypes.Structure):
     """bpe_gpu.h bpe_gpu_stream"""
+    _fields_ = [(n, ctypes.c_uint32) for n in ("seq_len", "flags", "bos_id", "eos_id", "pad_id")]
+
+
+class Whole(ctypes.Structure):
+    """bpe_gpu.h bpe_gpu_whole"""
     _fields_ = [(n, ctypes.c_uint32) for n in ("seq_len", "flags", "bos_id", "eos_id", "pad_id")]
 
 
@@ -307,6 +314,11 @@ def load():
     L.bpe_gpu_stream_info.argtypes = [vp]
     L.bpe_stream_check.argtypes = [stp, ctypes.c_char_p, sz]
     L.bpe_pack_stream_host.argtypes = [vp, sz, vp, sz, stp, vp, vp, vp, sz, ctypes.POINTER(sz), u64p]
+    whp = ctypes.POINTER(Whole)
+    L.bpe_gpu_pack_whole.argtypes = [vp, whp, vp, vp, vp, vp, vp, ctypes.c_int, sz, ctypes.POINTER(sz), u64p, u64p]
+    L.bpe_gpu_whole_info.argtypes = [vp]
+    L.bpe_whole_check.argtypes = [whp, ctypes.c_char_p, sz]
+    L.bpe_pack_whole_host.argtypes = [vp, sz, vp, sz, whp, vp, vp, vp, vp, vp, sz, ctypes.POINTER(sz), u64p, u64p]
     rwp = ctypes.POINTER(Rows)
     L.bpe_gpu_unpack_rows.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, sz, ctypes.c_uint32, sz, vp, ctypes.c_int, rwp,
                                       ctypes.POINTER(sz)]

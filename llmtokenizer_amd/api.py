@@ -678,6 +678,65 @@ def stream_info():
     return {"per_thread": int(out[0]), "per_block": int(out[1]), "per_grid": int(out[2]), "walk": int(out[3])}
 
 
+WHOLE_BOS, WHOLE_EOS = 1, 2  # bpe_gpu.h BPE_WHOLE_*
+
+
+def check_whole(seq_len, pad_id=0, bos_id=None, eos_id=None, flags=None):
+    """The description of whole-text rows (bpe_gpu.h bpe_gpu_whole) that pack_whole takes, checked by bpe_ex.h
+    bpe_whole_check: seq_len in 1 .. 2^24, the ids any uint32 (None: no BOS / EOS).  flags (for the tests): the flag
+    word as it is.  Raises BpeError with the code's text and a message that names the field.  No GPU."""
+    L = _lib.load()
+    vals = [int(seq_len), int(pad_id), int(bos_id or 0), int(eos_id or 0)]
+    f = (WHOLE_BOS if bos_id is not None else 0) | (WHOLE_EOS if eos_id is not None else 0) if flags is None else int(flags)
+    if any(not 0 <= v <= 0xFFFFFFFF for v in vals + [f]):
+        raise BpeError("whole: seq_len, pad_id, bos_id, eos_id and flags are uint32")
+    s = _lib.Whole(vals[0], f, vals[2], vals[3], vals[1])
+    msg = ctypes.create_string_buffer(400)
+    rc = L.bpe_whole_check(ctypes.byref(s), msg, len(msg))
+    if rc:
+        raise BpeError(f"check_whole: {L.bpe_gpu_strerror(rc).decode()} ({msg.value.decode(errors='replace')})")
+    return s
+
+
+def pack_whole_host(ids, text_off, seq_len, pad_id, bos_id=None, eos_id=None):
+    """Training rows that never split a text that fits one, on the host in plain loops (bpe_ex.h
+    bpe_pack_whole_host: the definition Engine.pack_whole is held to; the contract: bpe_gpu.h, "Whole-text rows"):
+    every text wrapped in bos_id / eos_id (None: without) and placed in order; a text that no longer fits the row
+    opens the next, a text longer than a row takes rows of its own, pad_id fills what is left.  Returns a dict:
+    rows, seg, pos uint32[R, seq_len] (seg 0xFFFFFFFF in a pad cell), text_row, text_col uint32[texts] (where every
+    text's first cell went), cells (the occupied cells) and n_long (the texts longer than a row).  No GPU."""
+    L = _lib.load()
+    s = check_whole(seq_len, pad_id, bos_id, eos_id)
+    ids = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
+    toff = _doc_offsets(text_off)
+    if toff.size < 1:
+        raise BpeError("pack_whole_host: text_off must hold texts + 1 entries")
+    vp, T = ctypes.c_void_p, toff.size - 1
+    R, N, nl = ctypes.c_size_t(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+    args = (ids.ctypes.data_as(vp) if ids.size else None, ids.size, toff.ctypes.data_as(vp), T, ctypes.byref(s))
+    tail = (ctypes.byref(R), ctypes.byref(N), ctypes.byref(nl))
+    rc = L.bpe_pack_whole_host(*args, None, None, None, None, None, 0, *tail)
+    if rc:  # (the description passed check_whole: what is left are the offsets and the row count)
+        raise BpeError(f"pack_whole_host: {L.bpe_gpu_strerror(rc).decode()} (text_off must run from 0 to the number "
+                       "of ids without falling, and the rows must number below 2^32)")
+    rows, seg, pos = (np.zeros((R.value, s.seq_len), dtype=np.uint32) for _ in range(3))
+    trow, tcol = np.zeros(T, dtype=np.uint32), np.zeros(T, dtype=np.uint32)
+    if R.value:
+        _lib.check(L.bpe_pack_whole_host(*args, *(a.ctypes.data_as(vp) for a in (rows, seg, pos, trow, tcol)), R.value,
+                                         *tail), "pack_whole_host")
+    return {"rows": rows, "seg": seg, "pos": pos, "text_row": trow, "text_col": tcol, "cells": int(N.value),
+            "n_long": int(nl.value)}
+
+
+def whole_info():
+    """{texts one lane of the placement kernels takes per step, texts per workgroup step, texts the largest grid takes
+    in one step (past that many a lane takes several), cells one lane of the four-cell fill takes per step}
+    (bpe_gpu_whole_info; no GPU; for the tests)"""
+    out = np.zeros(4, dtype=np.uint64)
+    _lib.check(_lib.load().bpe_gpu_whole_info(out.ctypes.data_as(ctypes.c_void_p)), "whole_info")
+    return {"per_thread": int(out[0]), "per_block": int(out[1]), "per_grid": int(out[2]), "fill_per_thread": int(out[3])}
+
+
 ROWS_PAD, ROWS_SKIP = 1, 2  # bpe_gpu.h BPE_ROWS_*
 
 
@@ -986,6 +1045,63 @@ class Engine:
             _lib.check(self.L.bpe_gpu_pack_stream(self.ctx, ctypes.byref(s), ptrs[0], ptrs[1], ptrs[2], 1, R, None, None),
                        "pack_stream")
         return tuple(out)
+
+    def whole_rows(self, seq_len, bos_id=None, eos_id=None):
+        """(R, N, n_long) of pack_whole() with these arguments: the rows, the occupied cells, and the texts longer
+        than a row, which are cut (the query of bpe_gpu_pack_whole: the placement runs on the device and is kept
+        for the pack_whole() that follows)"""
+        s = check_whole(seq_len, 0, bos_id, eos_id)
+        R, N, nl = ctypes.c_size_t(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        _lib.check(self.L.bpe_gpu_pack_whole(self.ctx, ctypes.byref(s), None, None, None, None, None, 0, 0, ctypes.byref(R),
+                                             ctypes.byref(N), ctypes.byref(nl)), "pack_whole")
+        return int(R.value), int(N.value), int(nl.value)
+
+    def pack_whole(self, seq_len, pad_id, bos_id=None, eos_id=None, segments=False, positions=False, placement=False,
+                   out=None):
+        """the resident ids of a text batch (mapped or not) as training rows that never split a text that fits one
+        (bpe_gpu_pack_whole; the contract: bpe_gpu.h, "Whole-text rows"): every text wrapped in bos_id / eos_id
+        (None: without) and placed in order; a text that no longer fits the row opens the next, a text longer than
+        a row is cut into rows of its own (whole_rows() counts them), pad_id fills what is left of any row.
+        Returns numpy arrays: rows uint32[R, seq_len], then with segments seg, with positions pos (as pack_stream),
+        and with placement text_row, text_col uint32[texts], the row and column of every text's first cell (what
+        cu_seqlens need); rows alone when nothing else is asked for.  out=(rows, seg or None, pos or None):
+        contiguous torch tensors of 32-bit integers, [R, seq_len] (R of whole_rows()), on this engine's device:
+        written on the device and returned as a tuple, with placement followed by text_row and text_col as torch
+        int32 tensors on the same device."""
+        s = check_whole(seq_len, pad_id, bos_id, eos_id)
+        R = self.whole_rows(seq_len, bos_id, eos_id)[0]
+        T = self.text_offsets().size - 1 if placement else 0
+        vp = ctypes.c_void_p
+        if out is None:
+            arrs = [np.zeros((R, s.seq_len), dtype=np.uint32) for _ in range(1 + bool(segments) + bool(positions))]
+            place = [np.zeros(T, dtype=np.uint32) for _ in range(2 if placement else 0)]
+            ptrs = [a.ctypes.data_as(vp) if a.size else None for a in arrs]
+            seg = ptrs[1] if segments else None
+            pos = ptrs[1 + bool(segments)] if positions else None
+            pl = [a.ctypes.data_as(vp) if a.size else None for a in place] or [None, None]
+            if R:
+                _lib.check(self.L.bpe_gpu_pack_whole(self.ctx, ctypes.byref(s), ptrs[0], seg, pos, pl[0], pl[1], 0, R, None,
+                                                     None, None), "pack_whole")
+            arrs += place
+            return tuple(arrs) if len(arrs) > 1 else arrs[0]
+        import torch
+        if not isinstance(out, (tuple, list)) or len(out) != 3 or out[0] is None:
+            raise BpeError("pack_whole: out must be (rows, seg or None, pos or None)")
+        for t in out:
+            if t is None:
+                continue
+            if (not isinstance(t, torch.Tensor) or not t.is_cuda or t.element_size() != 4 or t.is_floating_point()
+                    or tuple(t.shape) != (R, s.seq_len) or not t.is_contiguous()):
+                raise BpeError(f"pack_whole: out must hold contiguous 32-bit integer tensors of shape ({R}, {s.seq_len}) "
+                               "on the GPU")
+            if t.device != out[0].device:
+                raise BpeError("pack_whole: the tensors of out lie on different devices")
+        place = [torch.zeros(T, dtype=torch.int32, device=out[0].device) for _ in range(2 if placement else 0)]
+        torch.cuda.current_stream(out[0].device).synchronize()  # (the call writes on the context's stream)
+        ptrs = [vp(t.data_ptr()) if t is not None and t.numel() else None for t in list(out) + place] + [None, None]
+        if R:
+            _lib.check(self.L.bpe_gpu_pack_whole(self.ctx, ctypes.byref(s), *ptrs[:5], 1, R, None, None, None), "pack_whole")
+        return tuple(out) + tuple(place)
 
     def unpack_rows(self, rows, lens=None, pad_id=None, stop_ids=(), skip_ids=()):
         """the texts' ids of a grid of cells, cut on the device (bpe_gpu_unpack_rows; the contract: bpe_gpu.h, "Rows

@@ -35,6 +35,7 @@
 #include "texts.hip"
 #include "spans.hip"
 #include "stream.hip"
+#include "whole.hip"
 #include "rows.hip"
 #include "normalize.hip"
 
@@ -53,6 +54,7 @@ extern "C" int bpe_span_lens(const uint32_t *pairs, size_t n_merges, const bpe_g
                              uint32_t *out, size_t cap, size_t *count, char *msg, size_t msg_cap);
 // (bpe_ex.h, src/bpe_stream.c: the host definition of a packed stream's description)
 extern "C" int bpe_stream_check(const bpe_gpu_stream *s, char *msg, size_t msg_cap);
+extern "C" int bpe_whole_check(const bpe_gpu_whole *s, char *msg, size_t msg_cap);
 extern "C" int bpe_rows_check(const bpe_gpu_rows *desc, char *msg, size_t msg_cap);
 
 using namespace bpeamd;
@@ -347,6 +349,11 @@ struct bpe_gpu_ctx {
     // split_ready, split_n counts the break pieces too and DS_TX_PIECE / DS_TX_SPLIT hold what split_run left.
     bool tx_on = false;
     uint64_t tx_T = 0;
+    // the last placement of bpe_gpu_pack_whole over that batch's text_off: scratch slot DS_WH_CELL holds every text's
+    // first cell for row length whole_L and w = whole_w.  It goes where text_off goes: every assignment to ids_ready,
+    // docs_ready or tx_on clears whole_ready.
+    bool whole_ready = false;
+    uint64_t whole_L = 0, whole_w = 0, whole_R = 0, whole_long = 0;
     // the last bpe_gpu_unpack_rows: scratch slots DS_ROWS_IDS, DS_ROWS_OFF and DS_ROWS_BOUNDS hold rows_n ids of rows_B
     // rows.  Nothing but the next unpack and bpe_gpu_trim (which frees the slots) touches them.
     bool rows_ready = false;
@@ -528,6 +535,7 @@ void free_train(bpe_gpu_ctx *c, bool release = false) {
     c->retired.clear();
     c->merges_done = 0;  // h.merges (and h.mlog) are among the buffers released: bpe_gpu_fetch_merges must not read them
     c->spans_ready = false;
+    c->whole_ready = false;
     c->ids_ready = false;
     c->ids_mapped = false;
     c->docs_ready = false;
@@ -1854,6 +1862,7 @@ int compact_ids(bpe_gpu_ctx *c) {
     HIPCHK(hipStreamSynchronize(c->st));
     c->ids_len = tot;
     c->spans_ready = false;
+    c->whole_ready = false;
     c->ids_ready = true;
     return 0;
 }
@@ -2446,6 +2455,7 @@ int ew_run(bpe_gpu_ctx *c, const EwPlan &P, const uint32_t *d_img, uint32_t halo
     *ok = fl == 0;
     c->ids_len = total;
     c->spans_ready = false;
+    c->whole_ready = false;
     c->ids_ready = *ok;
     c->stats.enc_windows = nwin;
     return 0;
@@ -2654,6 +2664,7 @@ static int alloc_bytes(bpe_gpu_ctx *c, size_t n) {
     c->pres_valid = false;
     c->split_ready = false;  // the split's offsets describe the bytes replaced here
     c->tx_on = false;        // ... and so do a text batch's breaks
+    c->whole_ready = false;
     c->tx_T = 0;
     if (c->nf_spare && c->nf_spare_cap < n + 64) {  // (bpe_gpu_normalize's second buffer: kept while it fits the corpus)
         (void)hipFree(c->nf_spare);
@@ -2741,6 +2752,7 @@ int bpe_gpu_load_texts(bpe_gpu_ctx *c, const uint8_t *bytes, size_t n, const uin
     if ((r = ingest_presence(c, nres))) return r;
     HIPCHK(hipStreamSynchronize(c->st));
     c->tx_on = true;
+    c->whole_ready = false;
     c->tx_T = T;
     return 0;
 }
@@ -2995,6 +3007,7 @@ int bpe_gpu_encode(bpe_gpu_ctx *c, const uint32_t *pairs, size_t n_merges) {
     if (c->n0 == 0) {
         c->ids_len = 0;
         c->spans_ready = false;
+        c->whole_ready = false;
         c->ids_ready = true;
         return 0;
     }
@@ -3415,6 +3428,7 @@ int bpe_gpu_trim(bpe_gpu_ctx *c) {
     c->sp_M = 0;
     c->tx_on = false;
     c->tx_T = 0;
+    c->whole_ready = false;
     c->rows_ready = false;
     for (int k = 0; k < DS_COUNT; k++) {
         if (c->dscr[k]) (void)hipFree(c->dscr[k]);
@@ -3593,6 +3607,7 @@ static int encode_docs_run(bpe_gpu_ctx *c, const uint64_t *doc_off, size_t ndocs
         fprintf(stderr, "encode_docs host (ms): offset check %.2f, plan %.2f, first pass + fallback %.2f\n", t0 - t_chk,
                 t_plan - t0, t1 - t_plan);
     c->spans_ready = false;
+    c->whole_ready = false;
     c->ids_ready = true;
     c->docs_ready = true;
     c->docs_n = ndocs;
@@ -3725,6 +3740,7 @@ int bpe_gpu_map_ids(bpe_gpu_ctx *c, const bpe_gpu_vocab *vocab) {
     HIPCHK(hipStreamSynchronize(c->st));
     if (err) {  // (the ids are half rewritten: they are gone)
         c->spans_ready = false;
+        c->whole_ready = false;
         c->ids_ready = false;
         c->ids_mapped = false;
         c->docs_ready = false;
@@ -4036,6 +4052,147 @@ int bpe_gpu_pack_stream(bpe_gpu_ctx *c, const bpe_gpu_stream *s, uint32_t *rows,
         if ((r = d2h_staged(c, rows, d_rows, cells * 4))) return r;
         if (seg && (r = d2h_staged(c, seg, d_seg, cells * 4))) return r;
         if (pos && (r = d2h_staged(c, pos, d_pos, cells * 4))) return r;
+    }
+    HIPCHK(hipStreamSynchronize(c->st));
+    return 0;
+}
+
+// ------------------------------------------------ whole-text rows (whole.hip; the description's check: src/bpe_whole.c)
+
+int bpe_gpu_whole_info(uint64_t *out4) {
+    if (!out4) return BPE_GPU_EINVAL;
+    out4[0] = 1;
+    out4[1] = WH_T;
+    out4[2] = (uint64_t)WH_T * WH_GRID;
+    out4[3] = WH_VEC;
+    return 0;
+}
+
+}  // extern "C"
+
+// The placement of the resident text batch for row length L and w cells of BOS / EOS per text: DS_WH_CELL, whole_R and
+// whole_long, unless the context holds them already.  One synchronisation, to read R and n_long.
+static int whole_place(bpe_gpu_ctx *c, uint64_t L, uint64_t w) {
+    if (c->whole_ready && c->whole_L == L && c->whole_w == w) return 0;
+    c->whole_ready = false;
+    const uint64_t T = c->tx_T;
+    WhCount tot = {0, 0};
+    if (T) {
+        int r;
+        uint32_t *jump[2];
+        uint8_t *mark;
+        WhCount *first;
+        uint64_t *cell;
+        if ((r = dscratch(c, DS_WH_JUMP0, (T + 1) * 4, &jump[0])) || (r = dscratch(c, DS_WH_JUMP1, (T + 1) * 4, &jump[1])) ||
+            (r = dscratch(c, DS_WH_MARK, T, &mark)) || (r = dscratch(c, DS_WH_FIRST, (T + 1) * sizeof(WhCount), &first)) ||
+            (r = dscratch(c, DS_WH_CELL, T * 8, &cell)))
+            return r;
+        const uint64_t *toff = (const uint64_t *)c->dscr[DS_TX_IDOFF];
+        const uint32_t grid = (uint32_t)std::min<uint64_t>((T + WH_T) / WH_T, WH_GRID);
+        k_whole_next<<<grid, WH_T, 0, c->st>>>(toff, T, w, L, jump[0], jump[1], mark);
+        HIPCHK(hipGetLastError());
+        uint32_t rounds = 0;  // ceil(log2(T + 1)): 2^rounds >= T + 1, more than the orbit's members
+        while ((1ull << rounds) < T + 1) rounds++;
+        for (uint32_t i = 0; i < rounds; i++) {
+            k_whole_double<<<grid, WH_T, 0, c->st>>>(mark, jump[i & 1], jump[(i & 1) ^ 1], T);
+            HIPCHK(hipGetLastError());
+        }
+        auto cnt = rocprim::make_transform_iterator(rocprim::make_counting_iterator<uint64_t>(0), WhCountOf{mark, toff, T, w, L});
+        r = ROCPRIM_RUN(c, DS_WH_TMP, rocprim::exclusive_scan(tmp, tb, cnt, first, WhCount{0, 0}, T + 1, WhPlus(), c->st));
+        if (r) return r;
+        auto key = rocprim::make_transform_iterator(rocprim::make_counting_iterator<uint64_t>(0), WhOpenerOf{mark, T});
+        uint32_t *opener = jump[0];  // (the pointers have done their work)
+        r = ROCPRIM_RUN(c, DS_WH_TMP, rocprim::inclusive_scan(tmp, tb, key, opener, T, rocprim::maximum<uint32_t>(), c->st));
+        if (r) return r;
+        k_whole_place<<<grid, WH_T, 0, c->st>>>(toff, T, w, L, mark, first, opener, cell);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(&tot, first + T, sizeof tot, hipMemcpyDeviceToHost, c->st));
+        HIPCHK(hipStreamSynchronize(c->st));
+    }
+    c->whole_L = L;
+    c->whole_w = w;
+    c->whole_R = tot.rows;
+    c->whole_long = tot.longs;
+    c->whole_ready = true;
+    return 0;
+}
+
+extern "C" {
+
+int bpe_gpu_pack_whole(bpe_gpu_ctx *c, const bpe_gpu_whole *s, uint32_t *rows, uint32_t *seg, uint32_t *pos, uint32_t *text_row,
+                       uint32_t *text_col, int out_is_device, size_t rows_cap, size_t *n_rows, uint64_t *n_cells,
+                       uint64_t *n_long) {
+    if (!c) return BPE_GPU_EINVAL;
+    char msg[400];
+    int r;
+    if ((r = bpe_whole_check(s, msg, sizeof msg))) return fail(r, msg);
+    if (!c->tx_on) return fail(BPE_GPU_ESTATE, "pack_whole: the context holds no text batch (bpe_gpu_load_texts)");
+    if (!c->ids_ready || !c->docs_ready) return fail(BPE_GPU_ESTATE, "pack_whole: no ids: encode_split first");
+    const uint64_t T = c->tx_T, n = c->ids_len, L = s->seq_len;
+    const uint32_t b = (s->flags & BPE_WHOLE_BOS) ? 1u : 0u, w = b + ((s->flags & BPE_WHOLE_EOS) ? 1u : 0u);
+    HIPCHK(hipSetDevice(c->dev));
+    if ((r = whole_place(c, L, w))) return r;
+    const uint64_t R = c->whole_R;
+    if (n_rows) *n_rows = (size_t)R;
+    if (n_cells) *n_cells = n + T * w;  // (n and T are below 2^32 each)
+    if (n_long) *n_long = c->whole_long;
+    if (R > 0xFFFFFFFFull) {
+        snprintf(msg, sizeof msg, "pack_whole: %llu rows: 2^32 or more, which text_row cannot hold", (unsigned long long)R);
+        return fail(BPE_GPU_ERANGE, msg);
+    }
+    if (!rows) return 0;  // the query
+    if (rows_cap < R) {
+        snprintf(msg, sizeof msg, "pack_whole: rows_cap %zu is below the %llu rows of the batch", rows_cap, (unsigned long long)R);
+        return fail(BPE_GPU_EINVAL, msg);
+    }
+    const uint64_t cells = R * L;
+    uint32_t *d_rows = rows, *d_seg = seg, *d_pos = pos, *d_trow = text_row, *d_tcol = text_col;
+    if (out_is_device) {
+        for (const void *p : {(const void *)rows, (const void *)seg, (const void *)pos, (const void *)text_row, (const void *)text_col}) {
+            if (!p) continue;
+            hipPointerAttribute_t at;
+            if (hipPointerGetAttributes(&at, p) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != c->dev) {
+                (void)hipGetLastError();
+                return fail(BPE_GPU_EINVAL, "pack_whole: rows / seg / pos / text_row / text_col is no device pointer of the context's device");
+            }
+            if ((uintptr_t)p & 3u) return fail(BPE_GPU_EINVAL, "pack_whole: a pointer that is not 4-byte aligned");
+        }
+    } else {
+        // (each array begins 16-byte aligned in the buffer whenever the four-cell variant can run: cells * 4 is then a multiple of 16)
+        const uint64_t arrays = 1 + (seg ? 1 : 0) + (pos ? 1 : 0);
+        if ((r = dscratch(c, DS_WH_PACK, (cells * arrays + 2 * T) * 4, &d_rows))) return r;
+        d_seg = seg ? d_rows + cells : nullptr;
+        d_pos = pos ? d_rows + cells * (seg ? 2 : 1) : nullptr;
+        d_trow = text_row ? d_rows + cells * arrays : nullptr;
+        d_tcol = text_col ? d_rows + cells * arrays + T : nullptr;
+    }
+    if (T && (d_trow || d_tcol)) {
+        const uint32_t grid = (uint32_t)std::min<uint64_t>((T + WH_T - 1) / WH_T, WH_GRID);
+        k_whole_rowcol<<<grid, WH_T, 0, c->st>>>((const uint64_t *)c->dscr[DS_WH_CELL], T, L, d_trow, d_tcol);
+        HIPCHK(hipGetLastError());
+    }
+    if (cells) {
+        const bool vec = L % WH_VEC == 0 && (((uintptr_t)d_rows | (uintptr_t)d_seg | (uintptr_t)d_pos) & 15u) == 0;
+        // a workgroup takes `steps` consecutive tiles: one while the cells fit WH_FILL_GRID workgroups, more past that
+        const uint64_t tile = (uint64_t)WH_T * (vec ? WH_VEC : 1), tiles = (cells + tile - 1) / tile;
+        const uint64_t steps = (tiles + WH_FILL_GRID - 1) / WH_FILL_GRID;
+        const uint32_t grid = (uint32_t)((tiles + steps - 1) / steps);
+        const uint32_t *ids = c->h.ids_out;
+        const uint64_t *toff = (const uint64_t *)c->dscr[DS_TX_IDOFF], *cell = (const uint64_t *)c->dscr[DS_WH_CELL];
+        if (vec)
+            k_fill_whole<true><<<grid, WH_T, 0, c->st>>>(ids, n, toff, cell, T, cells, steps, (uint32_t)L, w, b, s->bos_id, s->eos_id,
+                                                         s->pad_id, d_rows, d_seg, d_pos);
+        else
+            k_fill_whole<false><<<grid, WH_T, 0, c->st>>>(ids, n, toff, cell, T, cells, steps, (uint32_t)L, w, b, s->bos_id, s->eos_id,
+                                                          s->pad_id, d_rows, d_seg, d_pos);
+        HIPCHK(hipGetLastError());
+    }
+    if (!out_is_device) {
+        if (cells && (r = d2h_staged(c, rows, d_rows, cells * 4))) return r;
+        if (cells && seg && (r = d2h_staged(c, seg, d_seg, cells * 4))) return r;
+        if (cells && pos && (r = d2h_staged(c, pos, d_pos, cells * 4))) return r;
+        if (T && text_row && (r = d2h_staged(c, text_row, d_trow, T * 4))) return r;
+        if (T && text_col && (r = d2h_staged(c, text_col, d_tcol, T * 4))) return r;
     }
     HIPCHK(hipStreamSynchronize(c->st));
     return 0;

@@ -681,6 +681,13 @@ enum DScr {
     DS_SPN_OUT,          // bpe_gpu_token_spans: the spans [ids][2]; stays with the ids
     DS_SPN_PACK,         // bpe_gpu_pack_spans: the rows of a call with a host pointer
     DS_STR_PACK,         // bpe_gpu_pack_stream: rows, seg and pos of a call with host pointers
+    DS_WH_JUMP0,         // bpe_gpu_pack_whole: next[] and the doubled pointers, ping [T + 1]; then every text's opener
+    DS_WH_JUMP1,         // ... pong
+    DS_WH_MARK,          // bpe_gpu_pack_whole: a byte per text, set for a row opener
+    DS_WH_FIRST,         // bpe_gpu_pack_whole: the scanned WhCount: every opener's first row [T + 1]
+    DS_WH_TMP,           // bpe_gpu_pack_whole: rocprim temporary of its two scans
+    DS_WH_CELL,          // bpe_gpu_pack_whole: every text's first cell [T]; stays with the ids (whole_ready)
+    DS_WH_PACK,          // bpe_gpu_pack_whole: rows, seg, pos and the placement of a call with host pointers
     DS_ROWS_IN,          // bpe_gpu_unpack_rows: the rows of a call with a host pointer
     DS_ROWS_LENS,        // bpe_gpu_unpack_rows: ... and its lens
     DS_ROWS_SKIP,        // bpe_gpu_unpack_rows: the sorted skip list, filled up to a power of two

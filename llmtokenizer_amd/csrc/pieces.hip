@@ -405,6 +405,7 @@ int bpe_gpu_encode_split(bpe_gpu_ctx *c, const uint32_t *pairs, size_t n_merges)
     int r = encode_docs_run(c, nullptr, c->split_n, pairs, n_merges, now_ms());
     if (r || (!M && !tx)) return r;
     if (tx) c->docs_ready = false;  // (until the texts' offsets below are written)
+    c->whole_ready = false;
     if (M && (r = encode_split_specials(c, M, n_merges, tx))) return r;
     return tx ? encode_split_texts(c) : 0;
 }

@@ -537,7 +537,7 @@ class Tokenizer:
         return int(self.vocab.special_ids[specials.index(name)])
 
     def encode_packed(self, texts, seq_len, pad_id, bos=None, eos=None, drop_last=False, return_segments=False,
-                      return_positions=False, return_tensors=None):
+                      return_positions=False, return_tensors=None, whole=False, return_placement=False):
         """Encode a list of texts as encode_batch() does and lay the ids out for training (Engine.pack_stream; the
         contract: bpe_gpu.h, "Packed streams"): every text wrapped in bos / eos (None: without; an int is taken as
         a vocabulary id, a str or bytes must be one of vocab.specials and stands for its id), the texts joined end to
@@ -547,11 +547,23 @@ class Tokenizer:
         the batch, 0xFFFFFFFF in a pad cell, pos (return_positions) the cell's position in its text's stretch of the
         row, and N the cells of the stream (rows.reshape(-1)[:N] is the stream, the rest pad).
         return_tensors="pt": torch int32 tensors on the tokenizer's device, filled on the device without fetching the
-        ids to the host (a pad cell's seg reads -1)."""
+        ids to the host (a pad cell's seg reads -1).
+        whole=True: rows that never split a text that fits one (Engine.pack_whole; the contract: bpe_gpu.h,
+        "Whole-text rows"): the texts are placed in order, a text that no longer fits the row opens the next, and a
+        text longer than seq_len is cut into rows of its own.  Any row may end in pad cells, so drop_last is
+        refused; N counts the occupied cells, which no longer lie at the front.  return_placement (whole only):
+        text_row and text_col, uint32[texts], follow pos: the row and column of every text's first cell."""
         if return_tensors not in (None, "pt"):
             raise BpeError(f"encode_packed: return_tensors {return_tensors!r} (None or \"pt\")")
         bos_id, eos_id = self._special_id(bos, "bos"), self._special_id(eos, "eos")
-        api.check_stream(seq_len, pad_id, bos_id, eos_id, drop_last)  # (before any work)
+        if whole and drop_last:
+            raise BpeError("encode_packed: whole=True pads any row, drop_last has no meaning with it")
+        if return_placement and not whole:
+            raise BpeError("encode_packed: return_placement goes with whole=True")
+        if whole:
+            api.check_whole(seq_len, pad_id, bos_id, eos_id)  # (before any work)
+        else:
+            api.check_stream(seq_len, pad_id, bos_id, eos_id, drop_last)
         if return_tensors == "pt":
             import torch
             if not torch.cuda.is_available():  # (see encode_batch)
@@ -562,6 +574,16 @@ class Tokenizer:
         e.split(v.rule, v.specials or None)
         e.encode_split(v.merges)
         e.map_ids(v)
+        if whole:
+            R, N, _ = e.whole_rows(seq_len, bos_id, eos_id)
+            if return_tensors is None:
+                out = e.pack_whole(seq_len, pad_id, bos_id, eos_id, return_segments, return_positions, return_placement)
+                return (out if isinstance(out, tuple) else (out,)) + (N,)
+            dev = torch.device("cuda", self.device)
+            new = lambda: torch.empty((R, int(seq_len)), dtype=torch.int32, device=dev)  # noqa: E731
+            out = e.pack_whole(seq_len, pad_id, bos_id, eos_id, placement=return_placement,
+                               out=(new(), new() if return_segments else None, new() if return_positions else None))
+            return tuple(t for t in out if t is not None) + (N,)
         R, N = e.stream_rows(seq_len, bos_id, eos_id, drop_last)
         if return_tensors is None:
             out = e.pack_stream(seq_len, pad_id, bos_id, eos_id, drop_last, return_segments, return_positions)
