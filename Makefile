@@ -59,7 +59,11 @@ COBJ_ROWS := $(patsubst $(PKG)/src/%.c,$(BUILD)/%.o,$(CSRC_ROWS))
 # csrc/unicode_nfc.h; no engine call)
 CSRC_NORM := $(PKG)/src/bpe_normalize.c
 COBJ_NORM := $(patsubst $(PKG)/src/%.c,$(BUILD)/%.o,$(CSRC_NORM))
-HIPDEPS := $(wildcard $(PKG)/csrc/*.hip $(PKG)/csrc/*.h) $(PKG)/src/bpe_split_presets.h $(PKG)/src/bpe_o200k_rule.h $(PKG)/src/bpe_nfc_rule.h include/bpe_gpu.h
+# the encoder choice: src/bpe_encoder.c, the entry points over bpe_gpu_encode_docs_mode / bpe_gpu_encode_split_mode,
+# which none of the models above has
+CSRC_ENC := $(PKG)/src/bpe_encoder.c
+COBJ_ENC := $(patsubst $(PKG)/src/%.c,$(BUILD)/%.o,$(CSRC_ENC))
+HIPDEPS :=$(wildcard $(PKG)/csrc/*.hip $(PKG)/csrc/*.h) $(PKG)/src/bpe_split_presets.h $(PKG)/src/bpe_o200k_rule.h $(PKG)/src/bpe_nfc_rule.h include/bpe_gpu.h
 
 all: $(PKG)/libbpe_amd.so tools/bpe_main oracle
 
@@ -72,7 +76,7 @@ $(BUILD)/engine.o: $(HIPDEPS) | $(BUILD)
 $(BUILD)/%.o: $(PKG)/src/%.c $(wildcard include/*.h $(PKG)/src/*.h $(PKG)/csrc/unicode_classes.h $(PKG)/csrc/unicode_case_classes.h $(PKG)/csrc/unicode_nfc.h) | $(BUILD)
 	$(CC) $(CFLAGS) -c $< -o $@
 
-$(PKG)/libbpe_amd.so: $(BUILD)/engine.o $(COBJ) $(COBJ_GPU) $(COBJ_TS) $(COBJ_SP) $(COBJ_SPECIAL) $(COBJ_VOCAB) $(COBJ_TEXTS) $(COBJ_SPANS) $(COBJ_STREAM) $(COBJ_WHOLE) $(COBJ_ROWS) $(COBJ_NORM)
+$(PKG)/libbpe_amd.so: $(BUILD)/engine.o $(COBJ) $(COBJ_GPU) $(COBJ_TS) $(COBJ_SP) $(COBJ_SPECIAL) $(COBJ_VOCAB) $(COBJ_TEXTS) $(COBJ_SPANS) $(COBJ_STREAM) $(COBJ_WHOLE) $(COBJ_ROWS) $(COBJ_NORM) $(COBJ_ENC)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -lm -ldl -lpthread
 
 tools/bpe_main: tools/bpe_main.c $(PKG)/libbpe_amd.so

@@ -127,6 +127,15 @@ int bpe_split_offsets_host_special(int preset, const uint8_t *cls, const uint16_
 uint32_t *bpe_encode_split_special(const uint8_t *bytes, size_t n, int preset, const uint8_t *cls, const uint16_t *brk,
                                    const bpe_gpu_specials *specials, dyn_arr_t *pair_arr, int device, size_t *len,
                                    uint64_t **id_off, uint64_t **byte_off, size_t *ndocs);
+/* bpe_encode_docs and bpe_encode_split_special (specials may be NULL: none) with the device encoder chosen:
+ * mode is BPE_ENC_WINDOW (what those two do), BPE_ENC_PIECE or BPE_ENC_AUTO (bpe_gpu.h, bpe_gpu_encode_docs_mode).
+ * The ids are the same under every mode; lists beyond the window encoder's limits stay on the device under
+ * the other two.  Results and ownership as bpe_encode_docs / bpe_encode_split. */
+uint32_t *bpe_encode_docs_mode(const uint8_t *bytes, size_t n, const uint64_t *doc_off, size_t ndocs, dyn_arr_t *pair_arr,
+                               int device, int mode, size_t *len, uint64_t **id_off);
+uint32_t *bpe_encode_split_mode(const uint8_t *bytes, size_t n, int preset, const uint8_t *cls, const uint16_t *brk,
+                                const bpe_gpu_specials *specials, dyn_arr_t *pair_arr, int device, int mode, size_t *len,
+                                uint64_t **id_off, uint64_t **byte_off, size_t *ndocs);
 /* bpe_train_split / bpe_train_split_preset with specials: the special pieces are no part of the corpus */
 dyn_arr_t *bpe_train_split_special(const uint8_t *bytes, size_t n, int preset, const uint8_t *cls, const uint16_t *brk,
                                    const bpe_gpu_specials *specials, long max_merges, int device);

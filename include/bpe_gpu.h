@@ -76,7 +76,8 @@ typedef struct {
     uint64_t hot_mode;        /* 0 level summaries, 1 hot set, 2 hot set given up mid-run */
     uint64_t hot_scanned;     /* hot-set entries reduced, summed over the merges */
     uint64_t enc_path;        /* encode: 1 window-local replay, 3 the same after its wide-halo
-                                 retry, 2 global batched replay                 */
+                                 retry, 2 global batched replay, 4 piece-local replay
+                                 (document batches under BPE_ENC_PIECE / BPE_ENC_AUTO) */
     uint64_t enc_windows;     /* encode: windows replayed (window path)           */
     uint64_t relists;         /* training: byte-pair position lists rebuilt       */
     uint64_t batches;         /* training: merge batches (several merges per scan/apply pair) */
@@ -244,7 +245,23 @@ int bpe_gpu_encode_docs(bpe_gpu_ctx *ctx, const uint64_t *doc_off, size_t ndocs,
    a bpe_gpu_encode or a training afterwards leaves ids without documents, and this call, bpe_gpu_docs_info and
    bpe_gpu_token_spans then return BPE_GPU_ESTATE. */
 int bpe_gpu_fetch_doc_offsets(bpe_gpu_ctx *ctx, uint64_t *out, size_t cap, size_t *count);
-/* out8 = {ndocs, docs through the fallback, windows, windows failed, core, halo, 0, 0} */
+/* Which device encoder a document batch takes.  BPE_ENC_WINDOW: the window encoder when the merge list has a
+   plan for it (at most 65,279 merges in at most 256 layers), else every document alone through bpe_gpu_encode;
+   what bpe_gpu_encode_docs and bpe_gpu_encode_split do.  BPE_ENC_PIECE: the piece-local replay, whose cost
+   follows the length of a document and not the list: any valid list whose ids (256 + n_merges) stay within
+   bpe_gpu_piece_info's limit, BPE_GPU_ERANGE beyond it; a document longer than a tile takes goes alone through
+   bpe_gpu_encode and is counted in bpe_gpu_docs_info.  BPE_ENC_AUTO: the window encoder when there is a
+   plan, else the piece-local replay, else every document alone.  The ids are the same whichever runs;
+   stats.enc_path tells which did: 1 the windows, 4 the piece-local replay, 2 neither. */
+enum { BPE_ENC_WINDOW = 0, BPE_ENC_PIECE = 1, BPE_ENC_AUTO = 2 };
+int bpe_gpu_encode_docs_mode(bpe_gpu_ctx *ctx, const uint64_t *doc_off, size_t ndocs,
+                             const uint32_t *pairs, size_t n_merges, int mode);
+/* The piece-local replay's geometry (no GPU; for the host-side tests):
+   out4 = {positions of a tile, its core (a tile takes the documents that start in its core bytes),
+   bytes of the longest document a tile takes, ids (256 + merges) a list may reach} */
+int bpe_gpu_piece_info(uint64_t *out4);
+/* out8 = {ndocs, docs through the fallback, windows, windows failed, core, halo,
+   tiles of the piece-local replay, the largest number of rounds (merges of one document) any tile ran} */
 int bpe_gpu_docs_info(bpe_gpu_ctx *ctx, uint64_t *out8);
 /* bpe_gpu_decode plus byte_off[0..ndocs] (bytes of document d = out[byte_off[d], byte_off[d+1])) */
 int bpe_gpu_decode_docs(bpe_gpu_ctx *ctx, const uint32_t *ids, size_t len, const uint64_t *id_off,
@@ -449,6 +466,8 @@ int bpe_gpu_fetch_split_offsets(bpe_gpu_ctx *ctx, uint64_t *out, size_t cap, siz
    bpe_gpu_fetch_ids / _fetch_ids_range / _ids_checksum / _fetch_doc_offsets / _docs_info / _get_stats
    serve what bpe_gpu_encode_docs leaves for the same offsets */
 int bpe_gpu_encode_split(bpe_gpu_ctx *ctx, const uint32_t *pairs, size_t n_merges);
+/* ... with the encoder chosen (BPE_ENC_*, see bpe_gpu_encode_docs_mode) */
+int bpe_gpu_encode_split_mode(bpe_gpu_ctx *ctx, const uint32_t *pairs, size_t n_merges, int mode);
 
 /* ------------------------------------------------------------------------
  * Training on the pieces of the last split: merges that never cross a piece

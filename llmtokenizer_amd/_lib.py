@@ -40,7 +40,8 @@ EXPORTS = [
     "bpe_gpu_fetch_events", "bpe_gpu_trim",
     # bpe_gpu.h: document batches
     "bpe_gpu_encode_docs", "bpe_gpu_fetch_doc_offsets", "bpe_gpu_docs_info", "bpe_gpu_decode_docs",
-    "bpe_gpu_docs_window",
+    "bpe_gpu_docs_window", "bpe_gpu_encode_docs_mode", "bpe_gpu_encode_split_mode", "bpe_gpu_piece_info",
+    "bpe_encode_docs_mode", "bpe_encode_split_mode",
     # bpe_gpu.h: splitting the resident bytes
     "bpe_gpu_split_rule", "bpe_gpu_split_info", "bpe_gpu_split", "bpe_gpu_fetch_split_offsets", "bpe_gpu_encode_split",
     "bpe_gpu_split_preset",
@@ -240,6 +241,12 @@ def load():
     L.bpe_encode_docs.argtypes = [vp, sz, vp, sz, ctypes.POINTER(DynArr), ctypes.c_int, ctypes.POINTER(sz),
                                   ctypes.POINTER(u64p)]
     L.bpe_encode_docs.restype = u32p
+    L.bpe_gpu_encode_docs_mode.argtypes = [vp, vp, sz, vp, sz, ctypes.c_int]
+    L.bpe_gpu_encode_split_mode.argtypes = [vp, vp, sz, ctypes.c_int]
+    L.bpe_gpu_piece_info.argtypes = [vp]
+    L.bpe_encode_docs_mode.argtypes = [vp, sz, vp, sz, ctypes.POINTER(DynArr), ctypes.c_int, ctypes.c_int,
+                                       ctypes.POINTER(sz), ctypes.POINTER(u64p)]
+    L.bpe_encode_docs_mode.restype = u32p
     L.bpe_decode_docs.argtypes = [vp, sz, vp, sz, ctypes.POINTER(DynArr), ctypes.c_int, ctypes.POINTER(sz),
                                   ctypes.POINTER(u64p)]
     L.bpe_decode_docs.restype = ctypes.c_void_p
@@ -279,6 +286,10 @@ def load():
                                            ctypes.POINTER(sz), ctypes.POINTER(u64p), ctypes.POINTER(u64p),
                                            ctypes.POINTER(sz)]
     L.bpe_encode_split_special.restype = u32p
+    L.bpe_encode_split_mode.argtypes = [vp, sz, ctypes.c_int, vp, vp, spp, ctypes.POINTER(DynArr), ctypes.c_int, ctypes.c_int,
+                                        ctypes.POINTER(sz), ctypes.POINTER(u64p), ctypes.POINTER(u64p),
+                                        ctypes.POINTER(sz)]
+    L.bpe_encode_split_mode.restype = u32p
     L.bpe_train_split_special.argtypes = [vp, sz, ctypes.c_int, vp, vp, spp, ctypes.c_long, ctypes.c_int]
     L.bpe_train_split_special.restype = ctypes.POINTER(DynArr)
     L.bpe_decode_docs_special.argtypes = [vp, sz, vp, sz, ctypes.POINTER(DynArr), spp, ctypes.c_int, ctypes.POINTER(sz),

@@ -148,11 +148,37 @@ def _doc_offsets(offsets):
     return np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
 
 
-def encode_batch(docs, merges, device=0):
+# bpe_gpu.h BPE_ENC_WINDOW / BPE_ENC_PIECE / BPE_ENC_AUTO: the device encoder of a document batch
+ENCODERS = {"window": 0, "piece": 1, "auto": 2}
+
+
+def _encoder(name):
+    if name not in ENCODERS:
+        raise BpeError(f"no encoder {name!r} (have {sorted(ENCODERS)})")
+    return ENCODERS[name]
+
+
+PIECE_INFO = ("tile", "core", "piece_max", "max_ids")
+
+
+def piece_info():
+    """The piece-local replay's geometry (bpe_gpu_piece_info): the positions of a tile, its core (a tile takes
+    the documents that start in its core bytes), the bytes of the longest document a tile takes (longer ones go
+    through the per-document fallback) and the ids, 256 + merges, a list may reach.  No GPU."""
+    out = np.zeros(4, dtype=np.uint64)
+    _lib.check(_lib.load().bpe_gpu_piece_info(out.ctypes.data_as(ctypes.c_void_p)), "piece_info")
+    return {k: int(out[i]) for i, k in enumerate(PIECE_INFO)}
+
+
+def encode_batch(docs, merges, device=0, encoder="window"):
     """Encode a batch of documents (bytes-like objects) in one pass: no merge
     crosses a document boundary.  Returns (ids, offsets): ids[offsets[d]:offsets[d + 1]]
-    equals encode(docs[d], merges); offsets is uint64 of length len(docs) + 1."""
+    equals encode(docs[d], merges); offsets is uint64 of length len(docs) + 1.
+    encoder: "window" (merge lists within the window encoder's limits run on it, others document by
+    document), "piece" (the piece-local replay: any list up to piece_info()["max_ids"] ids) or "auto"
+    (the first that applies); the ids are the same."""
     L = _lib.load()
+    mode = _encoder(encoder)
     docs = [bytes(d) for d in docs]
     buf = np.frombuffer(b"".join(docs), dtype=np.uint8)
     off = np.zeros(len(docs) + 1, dtype=np.uint64)
@@ -161,8 +187,12 @@ def encode_batch(docs, merges, device=0):
     n = ctypes.c_size_t(0)
     ido = ctypes.POINTER(ctypes.c_uint64)()
     try:
-        p = L.bpe_encode_docs(buf.ctypes.data_as(ctypes.c_void_p), buf.size, off.ctypes.data_as(ctypes.c_void_p),
-                              len(docs), arr, int(device), ctypes.byref(n), ctypes.byref(ido))
+        if mode == ENCODERS["window"]:
+            p = L.bpe_encode_docs(buf.ctypes.data_as(ctypes.c_void_p), buf.size, off.ctypes.data_as(ctypes.c_void_p),
+                                  len(docs), arr, int(device), ctypes.byref(n), ctypes.byref(ido))
+        else:
+            p = L.bpe_encode_docs_mode(buf.ctypes.data_as(ctypes.c_void_p), buf.size, off.ctypes.data_as(ctypes.c_void_p),
+                                       len(docs), arr, int(device), mode, ctypes.byref(n), ctypes.byref(ido))
     finally:
         L.dyn_arr_free(arr)
     if not p:
@@ -364,7 +394,7 @@ def _rule_tables(rule):
     return cls, brk
 
 
-def encode_split(data: bytes, merges, rule="words", device=0, specials=None):
+def encode_split(data: bytes, merges, rule="words", device=0, specials=None, encoder="window"):
     """Split data into pieces on the GPU (rule: a preset name, "lines", "words",
     "gpt2", "gpt2_unicode", "cl100k" (the pre-tokenizer of cl100k_base and Llama 3) or "o200k" (that of o200k_base), or a (cls, brk) pair, see
     split_rule) and encode the pieces as documents.  Returns (ids,
@@ -372,8 +402,9 @@ def encode_split(data: bytes, merges, rule="words", device=0, specials=None):
     is data[byte_offsets[d]:byte_offsets[d + 1]] and its ids are
     ids[id_offsets[d]:id_offsets[d + 1]] == encode(piece d, merges).  With specials (a list of
     bytes-like objects, see check_specials) every occurrence of specials[j] is a piece of its own
-    with the one id 256 + len(merges) + j."""
+    with the one id 256 + len(merges) + j.  encoder: as in encode_batch."""
     L = _lib.load()
+    mode = _encoder(encoder)
     if specials is not None:
         check_specials(specials)
     gpt2 = _no_tables(rule)
@@ -384,7 +415,13 @@ def encode_split(data: bytes, merges, rule="words", device=0, specials=None):
     ido, bo = ctypes.POINTER(ctypes.c_uint64)(), ctypes.POINTER(ctypes.c_uint64)()
     vp = ctypes.c_void_p
     try:
-        if specials is not None:
+        if mode != ENCODERS["window"]:
+            sp = _Specials(specials) if specials is not None else None
+            preset, pc, pb, keep = _rule_args(rule)
+            p = L.bpe_encode_split_mode(buf.ctypes.data_as(vp), buf.size, preset, pc, pb, sp.ref if sp else None, arr,
+                                        int(device), mode, ctypes.byref(n), ctypes.byref(ido), ctypes.byref(bo),
+                                        ctypes.byref(nd))
+        elif specials is not None:
             sp = _Specials(specials)
             preset, pc, pb, keep = _rule_args(rule)
             p = L.bpe_encode_split_special(buf.ctypes.data_as(vp), buf.size, preset, pc, pb, sp.ref, arr, int(device),
@@ -1210,15 +1247,17 @@ class Engine:
         m = np.ascontiguousarray(merges, dtype=np.uint32).reshape(-1)
         _lib.check(self.L.bpe_gpu_encode(self.ctx, m.ctypes.data_as(ctypes.c_void_p), m.size // 2), "encode")
 
-    def encode_docs(self, offsets, merges):
+    def encode_docs(self, offsets, merges, encoder="window"):
         """encode the resident bytes as documents: document d is bytes
-        [offsets[d], offsets[d + 1]) (bpe_gpu_encode_docs); then ids(), doc_offsets(), docs_info()"""
+        [offsets[d], offsets[d + 1]) (bpe_gpu_encode_docs_mode); then ids(), doc_offsets(), docs_info().
+        encoder: "window", "piece" or "auto", as in api.encode_batch; stats()["enc_path"] tells which ran."""
         off = _doc_offsets(offsets)
         if off.size < 1:
             raise BpeError("encode_docs: offsets must hold ndocs + 1 entries")
         m = np.ascontiguousarray(merges, dtype=np.uint32).reshape(-1)
-        _lib.check(self.L.bpe_gpu_encode_docs(self.ctx, off.ctypes.data_as(ctypes.c_void_p), off.size - 1,
-                                              m.ctypes.data_as(ctypes.c_void_p), m.size // 2), "encode_docs")
+        _lib.check(self.L.bpe_gpu_encode_docs_mode(self.ctx, off.ctypes.data_as(ctypes.c_void_p), off.size - 1,
+                                                   m.ctypes.data_as(ctypes.c_void_p), m.size // 2, _encoder(encoder)),
+                   "encode_docs")
 
     def split(self, rule="words", specials=None):
         """split the resident bytes into pieces on the device (rule: a preset
@@ -1269,12 +1308,13 @@ class Engine:
                                                        n.value, ctypes.byref(n)), "fetch_special_pieces")
         return piece[: n.value], index[: n.value]
 
-    def encode_split(self, merges):
-        """encode_docs over the last split's resident offsets (bpe_gpu_encode_split);
+    def encode_split(self, merges, encoder="window"):
+        """encode_docs over the last split's resident offsets (bpe_gpu_encode_split_mode);
         then ids(), doc_offsets(), docs_info() as after encode_docs.  After a split with specials
         every special piece holds the one id 256 + len(merges) + j."""
         m = np.ascontiguousarray(merges, dtype=np.uint32).reshape(-1)
-        _lib.check(self.L.bpe_gpu_encode_split(self.ctx, m.ctypes.data_as(ctypes.c_void_p), m.size // 2), "encode_split")
+        _lib.check(self.L.bpe_gpu_encode_split_mode(self.ctx, m.ctypes.data_as(ctypes.c_void_p), m.size // 2,
+                                                    _encoder(encoder)), "encode_split")
 
     def train_split(self, max_merges=-1):
         """train on the pieces of the last split (bpe_gpu_train_split): the bytes, the
@@ -1324,7 +1364,7 @@ class Engine:
                                                     ctypes.byref(n)), "fetch_doc_offsets")
         return out
 
-    DOCS_INFO = ("ndocs", "docs_fallback", "windows", "windows_failed", "core", "halo")
+    DOCS_INFO = ("ndocs", "docs_fallback", "windows", "windows_failed", "core", "halo", "tiles", "rounds")
 
     def docs_info(self):
         """counters of the last encode_docs (bpe_gpu_docs_info)"""

@@ -27,6 +27,7 @@
 #include "encode.hip"
 #include "encode_win.hip"
 #include "encode_docs.hip"
+#include "encode_piece.hip"
 #include "split.hip"
 #include "split_o200k.hip"
 #include "train_split.hip"
@@ -2561,6 +2562,101 @@ int ed_run(bpe_gpu_ctx *c, const EwPlan &P, const uint32_t *d_img, uint32_t halo
     return 0;
 }
 
+// The piece-local replay's rank tables (encode_piece.hip), as one host image:
+//   bp[65536] (byte pair -> rank) | ht[H] (a << 42 | b << 21 | rank + 1; 0: empty)
+// Ranks and ids are the list's own.  As in ew_plan, a record that names an id at
+// or above its own never matches and stays out, and of a repeated pair the
+// first record is the one that can match.  H is a power of two, at most 1/4 full.
+struct EpTable {
+    uint32_t H = 0;
+    size_t words = 0;  // of the image: 65536 + 2 * H
+};
+
+EpTable ep_table(const uint32_t *pairs, size_t m, std::vector<uint32_t> &img) {
+    EpTable T;
+    size_t keys = 0;
+    for (size_t r = 0; r < m; r++) keys += (pairs[2 * r] | pairs[2 * r + 1]) >= 256;
+    T.H = 64;
+    while (T.H < 4 * keys) T.H <<= 1;
+    T.words = 65536 + 2 * (size_t)T.H;
+    img.assign(T.words, 0);
+    std::fill(img.begin(), img.begin() + 65536, EP_NONE);
+    std::vector<uint64_t> ht(T.H, 0);
+    for (size_t r = 0; r < m; r++) {
+        const uint64_t u = pairs[2 * r], v = pairs[2 * r + 1];
+        if (u >= 256 + r || v >= 256 + r) continue;
+        if ((u | v) < 256) {
+            uint32_t &e = img[(u << 8) | v];
+            if (e == EP_NONE) e = (uint32_t)r;
+            continue;
+        }
+        const uint64_t key = (u << EP_ID_BITS) | v;
+        uint32_t s = (uint32_t)mix64(key) & (T.H - 1);
+        while (ht[s] && (ht[s] >> EP_ID_BITS) != key) s = (s + 1) & (T.H - 1);
+        if (!ht[s]) ht[s] = (key << EP_ID_BITS) | (r + 1);
+    }
+    memcpy(img.data() + 65536, ht.data(), (size_t)T.H * 8);
+    return T;
+}
+
+// Encode c's bytes as documents (d_doc[ndocs + 1] on the device) by the
+// piece-local replay (encode_piece.hip) into c's ids and id offsets, as ed_run
+// leaves them; *nlong = documents longer than EP_PIECE_MAX, which have no ids yet.
+int ep_run(bpe_gpu_ctx *c, const uint32_t *pairs, size_t n_merges, const uint64_t *d_doc, uint64_t ndocs, uint64_t *nlong,
+           uint64_t *tiles_out, uint64_t *rounds) {
+    const uint64_t n = c->n0, tiles = (n + EP_C - 1) / EP_C;
+    int r;
+    const EpTable T = ep_table(pairs, n_merges, c->ew_stage);
+    void *d_img;
+    if ((r = dscratch(c, DS_EP_TABLES, T.words * 4, &d_img))) return r;
+    HIPCHK(hipMemcpyAsync(d_img, c->ew_stage.data(), T.words * 4, hipMemcpyHostToDevice, c->st));
+    uint32_t *ids, *stage, *cnt, *tfirst, *tcnt, *ctl;
+    uint64_t *d_idoff;
+    if ((r = dalloc(c, &ids, std::max<uint64_t>(n, 1), false))) return r;
+    if ((r = dalloc(c, &stage, std::max<uint64_t>(n, 1), false))) return r;
+    if ((r = dalloc(c, &cnt, ndocs + 1))) return r;  // zeroed
+    if ((r = dalloc(c, &tfirst, std::max<uint64_t>(tiles, 1), false))) return r;
+    if ((r = dalloc(c, &tcnt, std::max<uint64_t>(tiles, 1), false))) return r;
+    if ((r = dalloc(c, &ctl, EPC_WORDS))) return r;  // zeroed
+    if ((r = dalloc(c, &d_idoff, ndocs + 1, false))) return r;
+    c->h.ids_out = ids;
+    c->d_idoff = d_idoff;
+    EncPieceArgs A{};
+    A.bytes = c->h.bytes;
+    A.n = n;
+    A.doc_off = d_doc;
+    A.ndocs = (uint32_t)ndocs;
+    A.hmask = T.H - 1;
+    A.bp = (const uint32_t *)d_img;
+    A.ht = (const unsigned long long *)((const uint32_t *)d_img + 65536);
+    A.stage = stage;
+    A.cnt = cnt;
+    A.tfirst = tfirst;
+    A.tcnt = tcnt;
+    A.ctl = ctl;
+    if (tiles) k_enc_piece<<<(uint32_t)tiles, EP_T, 0, c->st>>>(A);
+    HIPCHK(hipGetLastError());
+    r = ROCPRIM_RUN(c, DS_SCAN_TMP, rocprim::exclusive_scan(tmp, tb, cnt, d_idoff, (uint64_t)0, ndocs + 1, rocprim::plus<uint64_t>(), c->st));
+    if (r) return r;
+    if (tiles)
+        k_ep_gather<<<(uint32_t)((tiles + EPG_T / 64 - 1) / (EPG_T / 64)), EPG_T, 0, c->st>>>(stage, d_doc, d_idoff, tfirst, tcnt,
+                                                                                            tiles, ids);
+    HIPCHK(hipGetLastError());
+    uint32_t h[EPC_WORDS] = {};
+    uint64_t total = 0;
+    HIPCHK(hipMemcpyAsync(h, ctl, sizeof h, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipMemcpyAsync(&total, d_idoff + ndocs, 8, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipStreamSynchronize(c->st));
+    if (h[EPC_ERROR])
+        return fail(BPE_GPU_EINTERNAL, h[EPC_ERROR] & 2u ? "encode_piece: a tile ran more rounds than it has positions"
+                                                         : "encode_piece: a tile's documents do not fit it");
+    *nlong = h[EPC_LONG];
+    *tiles_out = tiles;
+    *rounds = h[EPC_ROUNDS];
+    c->ids_len = total;
+    return 0;
+}
+
 }  // namespace
 
 // ===================================================================== C-ABI
@@ -3491,7 +3587,10 @@ int bpe_gpu_docs_window(const uint64_t *doc_off, size_t ndocs, uint64_t n, uint3
 // the offsets are the split's, resident in c->d_split; the cold paths below
 // that read offsets on the host download them, and only they do).
 static int encode_docs_run(bpe_gpu_ctx *c, const uint64_t *doc_off, size_t ndocs, const uint32_t *pairs, size_t n_merges,
-                           double t_chk) {
+                           double t_chk, int mode) {
+    if (mode != BPE_ENC_WINDOW && mode != BPE_ENC_PIECE && mode != BPE_ENC_AUTO) return fail(BPE_GPU_EINVAL, "encode_docs: no such encoder mode");
+    const bool ep_fits = 256 + (uint64_t)n_merges <= EP_MAX_IDS;
+    if (mode == BPE_ENC_PIECE && !ep_fits) return fail(BPE_GPU_ERANGE, "encode_docs: the merge list's ids exceed the piece-local replay's 2^21");
     const uint64_t n = c->n0;
     const bool resident = doc_off == nullptr;
     std::vector<uint64_t> h_split;
@@ -3514,10 +3613,25 @@ static int encode_docs_run(bpe_gpu_ctx *c, const uint64_t *doc_off, size_t ndocs
     free_train(c);
     // first pass: every window of the concatenated stream (nothing else runs when none fails)
     std::vector<uint8_t> failed;  // documents for the fallback (sized when there are any)
-    uint64_t nfailed = 0, wfailed = 0, nwin = 0, core = 0, halo = 0;
+    uint64_t nfailed = 0, wfailed = 0, nwin = 0, core = 0, halo = 0, tiles = 0, rounds = 0;
     bool first_pass = false;
-    const EwPlan P = n ? ew_plan(pairs, n_merges, c->ew_stage) : EwPlan{};
+    const EwPlan P = n && mode != BPE_ENC_PIECE ? ew_plan(pairs, n_merges, c->ew_stage) : EwPlan{};
+    const bool piece = mode == BPE_ENC_PIECE || (mode == BPE_ENC_AUTO && n && !P.ok && ep_fits);
     const double t_plan = now_ms();
+    // the offsets on the device: the split's, or the caller's uploaded
+    const uint64_t *d_doc = c->d_split;
+    double ms_upload = 0;
+    if (!resident && (P.ok || piece)) {
+        const double tu = now_ms();
+        uint64_t *up;
+        if ((r = dalloc(c, &up, ndocs + 1, false))) return r;
+        HIPCHK(hipMemcpyAsync(up, doc_off, (ndocs + 1) * 8, hipMemcpyHostToDevice, c->st));
+        if (getenv_int("BPE_EW_PROF", 0)) {
+            HIPCHK(hipStreamSynchronize(c->st));
+            ms_upload = now_ms() - tu;
+        }
+        d_doc = up;
+    }
     if (P.ok) {
         void *d_img;
         if ((r = dscratch(c, DS_EW_TABLES, P.words * 4, &d_img))) return r;
@@ -3526,19 +3640,6 @@ static int encode_docs_run(bpe_gpu_ctx *c, const uint64_t *doc_off, size_t ndocs
         core = EW_W - 2 * halo;
         nwin = (n + core - 1) / core;
         std::vector<uint32_t> wfail;
-        const uint64_t *d_doc = c->d_split;
-        double ms_upload = 0;
-        if (!resident) {
-            const double tu = now_ms();
-            uint64_t *up;
-            if ((r = dalloc(c, &up, ndocs + 1, false))) return r;
-            HIPCHK(hipMemcpyAsync(up, doc_off, (ndocs + 1) * 8, hipMemcpyHostToDevice, c->st));
-            if (getenv_int("BPE_EW_PROF", 0)) {
-                HIPCHK(hipStreamSynchronize(c->st));
-                ms_upload = now_ms() - tu;
-            }
-            d_doc = up;
-        }
         if ((r = ed_run(c, P, (const uint32_t *)d_img, (uint32_t)halo, d_doc, ndocs, &wfailed, wfail, ms_upload))) return r;
         first_pass = true;
         if (wfailed && (r = host_offsets())) return r;
@@ -3549,6 +3650,16 @@ static int encode_docs_run(bpe_gpu_ctx *c, const uint64_t *doc_off, size_t ndocs
                 for (uint64_t w = doc_off[d] / core; w <= (doc_off[d + 1] - 1) / core && !failed[d]; w++) failed[d] = wfail[w] != 0;
                 nfailed += failed[d];
             }
+    } else if (piece) {
+        // the piece-local replay: only the documents longer than a tile takes are left for the fallback
+        if ((r = ep_run(c, pairs, n_merges, d_doc, ndocs, &nfailed, &tiles, &rounds))) return r;
+        first_pass = true;
+        if (nfailed) {
+            if ((r = host_offsets())) return r;
+            failed.assign(ndocs, 0);
+            nfailed = 0;
+            for (size_t d = 0; d < ndocs; d++) nfailed += failed[d] = doc_off[d + 1] - doc_off[d] > EP_PIECE_MAX;
+        }
     } else {
         // no plan (too many merges or layers), or no bytes: every document with bytes goes through the fallback
         if ((r = host_offsets())) return r;
@@ -3611,14 +3722,14 @@ static int encode_docs_run(bpe_gpu_ctx *c, const uint64_t *doc_off, size_t ndocs
     c->ids_ready = true;
     c->docs_ready = true;
     c->docs_n = ndocs;
-    const uint64_t info[8] = {ndocs, nfailed, nwin, wfailed, core, halo, 0, 0};
+    const uint64_t info[8] = {ndocs, nfailed, nwin, wfailed, core, halo, tiles, rounds};
     memcpy(c->docs_info, info, sizeof info);
     c->merges_done = 0;
-    c->stats.enc_path = first_pass ? 1 : 2;
+    c->stats.enc_path = piece ? 4 : first_pass ? 1 : 2;
     c->stats.enc_windows = nwin;
     c->stats.n_out = c->ids_len;
     c->stats.merges = n_merges;
-    c->stats.iterations = P.nb;
+    c->stats.iterations = piece ? rounds : P.nb;
     c->stats.occurrences = n - c->ids_len;
     c->stats.ms_train = t1 - t0;
     c->stats.ms_total = t1 - t0;
@@ -3627,7 +3738,8 @@ static int encode_docs_run(bpe_gpu_ctx *c, const uint64_t *doc_off, size_t ndocs
 
 extern "C" {
 
-int bpe_gpu_encode_docs(bpe_gpu_ctx *c, const uint64_t *doc_off, size_t ndocs, const uint32_t *pairs, size_t n_merges) {
+int bpe_gpu_encode_docs_mode(bpe_gpu_ctx *c, const uint64_t *doc_off, size_t ndocs, const uint32_t *pairs, size_t n_merges,
+                             int mode) {
     if (!c || !doc_off || (!pairs && n_merges)) return BPE_GPU_EINVAL;
     if (!c->loaded) return fail(BPE_GPU_ESTATE, "encode before load");
     if (c->tx_on) return fail(BPE_GPU_ESTATE, "encode_docs: the context holds a text batch (bpe_gpu_load_texts): its gap bytes are no text; split it and use bpe_gpu_encode_split");
@@ -3640,7 +3752,20 @@ int bpe_gpu_encode_docs(bpe_gpu_ctx *c, const uint64_t *doc_off, size_t ndocs, c
     bool dec = false;  // (a reduction, not an early exit: 10^7 offsets are checked at memory speed)
     for (size_t d = 0; d < ndocs; d++) dec |= doc_off[d] > doc_off[d + 1];
     if (dec) return fail(BPE_GPU_EINVAL, "encode_docs: offsets decrease");
-    return encode_docs_run(c, doc_off, ndocs, pairs, n_merges, t_chk);
+    return encode_docs_run(c, doc_off, ndocs, pairs, n_merges, t_chk, mode);
+}
+
+int bpe_gpu_encode_docs(bpe_gpu_ctx *c, const uint64_t *doc_off, size_t ndocs, const uint32_t *pairs, size_t n_merges) {
+    return bpe_gpu_encode_docs_mode(c, doc_off, ndocs, pairs, n_merges, BPE_ENC_WINDOW);
+}
+
+int bpe_gpu_piece_info(uint64_t *out4) {
+    if (!out4) return BPE_GPU_EINVAL;
+    out4[0] = EP_W;
+    out4[1] = EP_C;
+    out4[2] = EP_PIECE_MAX;
+    out4[3] = EP_MAX_IDS;
+    return 0;
 }
 
 int bpe_gpu_fetch_doc_offsets(bpe_gpu_ctx *c, uint64_t *out, size_t cap, size_t *count) {

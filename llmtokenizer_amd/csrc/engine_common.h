@@ -705,6 +705,7 @@ enum DScr {
     DS_NF_ENT,           // ... what the fallback knows of each (NfLong), sorted by start
     DS_NF_WS,            // ... and the entries it orders and composes
     DS_NF_BOFF,          // bpe_gpu_normalize: a text batch's new byte offsets, copied to DS_TX_BOFF at the end
+    DS_EP_TABLES,        // ep_run: the piece-local replay's rank tables (EpTable's image)
     DS_COUNT
 };
 // bpe_gpu_train_split takes its eight token-sized arrays as one run of slots

@@ -395,6 +395,10 @@ static int encode_split_specials(bpe_gpu_ctx *c, uint64_t M, size_t n_merges, bo
 static int encode_split_texts(bpe_gpu_ctx *c);
 
 int bpe_gpu_encode_split(bpe_gpu_ctx *c, const uint32_t *pairs, size_t n_merges) {
+    return bpe_gpu_encode_split_mode(c, pairs, n_merges, BPE_ENC_WINDOW);
+}
+
+int bpe_gpu_encode_split_mode(bpe_gpu_ctx *c, const uint32_t *pairs, size_t n_merges, int mode) {
     if (!c || (!pairs && n_merges)) return BPE_GPU_EINVAL;
     if (!c->loaded) return fail(BPE_GPU_ESTATE, "encode before load");
     if (!c->split_ready) return fail(BPE_GPU_ESTATE, "encode_split: no split of the loaded bytes");
@@ -402,7 +406,7 @@ int bpe_gpu_encode_split(bpe_gpu_ctx *c, const uint32_t *pairs, size_t n_merges)
     const bool tx = c->tx_on;
     const uint64_t M = c->sp_S || tx ? c->sp_M : 0;
     if (M && n_merges + 256 + c->sp_S > 0xFFFFFFFFull) return fail(BPE_GPU_ERANGE, "merge list too long for the specials' ids");
-    int r = encode_docs_run(c, nullptr, c->split_n, pairs, n_merges, now_ms());
+    int r = encode_docs_run(c, nullptr, c->split_n, pairs, n_merges, now_ms(), mode);
     if (r || (!M && !tx)) return r;
     if (tx) c->docs_ready = false;  // (until the texts' offsets below are written)
     c->whole_ready = false;

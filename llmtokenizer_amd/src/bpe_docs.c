@@ -3,14 +3,35 @@
  * over the engine's bpe_gpu_encode_docs / bpe_gpu_decode_docs, and
  * bpe_encode_split over bpe_gpu_split / bpe_gpu_encode_split, on the cached
  * engine contexts of bpe.c.  encode_split_with is its body with the split step
- * passed in: bpe_split_preset.c runs it over bpe_gpu_split_preset.
+ * passed in: bpe_split_preset.c runs it over bpe_gpu_split_preset.  encode_docs_body
+ * and encode_split_body take the encode step too: bpe_encoder.c runs them over
+ * bpe_gpu_encode_docs_mode / bpe_gpu_encode_split_mode.
  */
 #include "bpe_internal.h"
 
 #include <stdlib.h>
 
+static int encode_docs_window(bpe_gpu_ctx *ctx, const uint64_t *doc_off, size_t ndocs, const uint32_t *pairs, size_t k,
+                              int mode)
+{
+    (void)mode;
+    return bpe_gpu_encode_docs(ctx, doc_off, ndocs, pairs, k);
+}
+
+static int encode_split_window(bpe_gpu_ctx *ctx, const uint32_t *pairs, size_t k, int mode)
+{
+    (void)mode;
+    return bpe_gpu_encode_split(ctx, pairs, k);
+}
+
 uint32_t *bpe_encode_docs(const uint8_t *bytes, size_t n, const uint64_t *doc_off, size_t ndocs, dyn_arr_t *pair_arr,
                           int device, size_t *len, uint64_t **id_off)
+{
+    return encode_docs_body(bytes, n, doc_off, ndocs, pair_arr, device, encode_docs_window, 0, len, id_off);
+}
+
+uint32_t *encode_docs_body(const uint8_t *bytes, size_t n, const uint64_t *doc_off, size_t ndocs, dyn_arr_t *pair_arr,
+                           int device, bpe_encode_docs_fn encode, int mode, size_t *len, uint64_t **id_off)
 {
     if ((!bytes && n) || !doc_off || !pair_arr || !len || !id_off) return NULL;
     bpe_gpu_ctx *ctx = NULL;
@@ -21,7 +42,7 @@ uint32_t *bpe_encode_docs(const uint8_t *bytes, size_t n, const uint64_t *doc_of
     if (!pairs) return NULL;
     if ((rc = open_engine(device, &ctx))) goto done;
     if ((rc = bpe_gpu_load(ctx, bytes, n))) { report("load", rc); goto done; }
-    if ((rc = bpe_gpu_encode_docs(ctx, doc_off, ndocs, pairs, k))) { report("encode docs", rc); goto done; }
+    if ((rc = encode(ctx, doc_off, ndocs, pairs, k, mode))) { report("encode docs", rc); goto done; }
     if ((rc = bpe_gpu_fetch_ids(ctx, NULL, 0, &n_ids))) { report("fetch ids", rc); goto done; }
     ids = alloc_ids(n_ids);
     offs = malloc((ndocs + 1) * sizeof(uint64_t));
@@ -54,6 +75,13 @@ uint32_t *bpe_encode_split(const uint8_t *bytes, size_t n, const uint8_t *cls, c
 uint32_t *encode_split_with(const uint8_t *bytes, size_t n, bpe_split_fn split, const void *rule, dyn_arr_t *pair_arr,
                             int device, size_t *len, uint64_t **id_off, uint64_t **byte_off, size_t *ndocs)
 {
+    return encode_split_body(bytes, n, split, rule, pair_arr, device, encode_split_window, 0, len, id_off, byte_off, ndocs);
+}
+
+uint32_t *encode_split_body(const uint8_t *bytes, size_t n, bpe_split_fn split, const void *rule, dyn_arr_t *pair_arr,
+                            int device, bpe_encode_split_fn encode, int mode, size_t *len, uint64_t **id_off,
+                            uint64_t **byte_off, size_t *ndocs)
+{
     if ((!bytes && n) || !pair_arr || !len || !id_off || !ndocs) return NULL;
     bpe_gpu_ctx *ctx = NULL;
     size_t k = 0, n_ids = 0, n_off = 0, pieces = 0;
@@ -64,7 +92,7 @@ uint32_t *encode_split_with(const uint8_t *bytes, size_t n, bpe_split_fn split, 
     if ((rc = open_engine(device, &ctx))) goto done;
     if ((rc = bpe_gpu_load(ctx, bytes, n))) { report("load", rc); goto done; }
     if ((rc = split(ctx, rule, &pieces))) { report("split", rc); goto done; }
-    if ((rc = bpe_gpu_encode_split(ctx, pairs, k))) { report("encode split", rc); goto done; }
+    if ((rc = encode(ctx, pairs, k, mode))) { report("encode split", rc); goto done; }
     if ((rc = bpe_gpu_fetch_ids(ctx, NULL, 0, &n_ids))) { report("fetch ids", rc); goto done; }
     ids = alloc_ids(n_ids);
     offs = malloc((pieces + 1) * sizeof(uint64_t));

@@ -43,6 +43,17 @@ static inline int split_tables(bpe_gpu_ctx *ctx, const void *rule, size_t *piece
 BPE_PRIVATE uint32_t *encode_split_with(const uint8_t *bytes, size_t n, bpe_split_fn split, const void *rule,
                                         dyn_arr_t *pair_arr, int device, size_t *len, uint64_t **id_off,
                                         uint64_t **byte_off, size_t *ndocs);
+/* ... and the bodies of bpe_encode_docs and of encode_split_with with the encode step passed in too: bpe_gpu_encode_docs /
+ * bpe_gpu_encode_split there, their _mode forms with `mode` in bpe_encoder.c */
+typedef int (*bpe_encode_docs_fn)(bpe_gpu_ctx *ctx, const uint64_t *doc_off, size_t ndocs, const uint32_t *pairs, size_t k,
+                                  int mode);
+typedef int (*bpe_encode_split_fn)(bpe_gpu_ctx *ctx, const uint32_t *pairs, size_t k, int mode);
+BPE_PRIVATE uint32_t *encode_docs_body(const uint8_t *bytes, size_t n, const uint64_t *doc_off, size_t ndocs,
+                                       dyn_arr_t *pair_arr, int device, bpe_encode_docs_fn encode, int mode, size_t *len,
+                                       uint64_t **id_off);
+BPE_PRIVATE uint32_t *encode_split_body(const uint8_t *bytes, size_t n, bpe_split_fn split, const void *rule,
+                                        dyn_arr_t *pair_arr, int device, bpe_encode_split_fn encode, int mode, size_t *len,
+                                        uint64_t **id_off, uint64_t **byte_off, size_t *ndocs);
 /* the body of bpe_train_split and bpe_train_split_preset (bpe_train_split.c) */
 BPE_PRIVATE dyn_arr_t *train_split_with(const uint8_t *bytes, size_t n, bpe_split_fn split, const void *rule,
                                         long max_merges, int device);

@@ -410,10 +410,15 @@ class Vocab:
 
 class Tokenizer:
     """Encode to and decode from a vocabulary's own ids on one GPU: the split of vocab.rule around
-    vocab.specials, the merges applied inside the pieces, the ids rewritten on the device."""
+    vocab.specials, the merges applied inside the pieces, the ids rewritten on the device.  encoder: "auto"
+    (the window encoder for a merge list within its limits, which encodes as before; the piece-local replay
+    for the longer lists of cl100k_base, Llama 3, Qwen2 and o200k_base), "window" or "piece" (api.encode_batch)."""
 
-    def __init__(self, vocab, device=0):
+    def __init__(self, vocab, device=0, encoder="auto"):
+        if encoder not in api.ENCODERS:
+            raise api.BpeError(f"no encoder {encoder!r} (have {sorted(api.ENCODERS)})")
         self.vocab = vocab
+        self.encoder = encoder
         self.device = int(device)
         self._engine = None
 
@@ -461,7 +466,7 @@ class Tokenizer:
         e, v = self._eng(), self.vocab
         self._load("encode", data, unit, batch=False)
         e.split(v.rule, v.specials or None)
-        e.encode_split(v.merges)
+        e.encode_split(v.merges, encoder=self.encoder)
         e.map_ids(v)
         ids = e.ids()
         out = (ids, e.doc_offsets(), e.split_offsets()) if return_offsets else (ids,)
@@ -507,7 +512,7 @@ class Tokenizer:
         e, v = self._eng(), self.vocab
         n_texts = self._load("encode_batch", texts, unit)
         e.split(v.rule, v.specials or None)
-        e.encode_split(v.merges)
+        e.encode_split(v.merges, encoder=self.encoder)
         e.map_ids(v)
         if max_length is None:
             out = (e.ids(), e.text_offsets())
@@ -572,7 +577,7 @@ class Tokenizer:
         e, v = self._eng(), self.vocab
         self._load("encode_packed", texts)
         e.split(v.rule, v.specials or None)
-        e.encode_split(v.merges)
+        e.encode_split(v.merges, encoder=self.encoder)
         e.map_ids(v)
         if whole:
             R, N, _ = e.whole_rows(seq_len, bos_id, eos_id)
