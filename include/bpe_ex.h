@@ -128,7 +128,7 @@ uint32_t *bpe_encode_split_special(const uint8_t *bytes, size_t n, int preset, c
                                    const bpe_gpu_specials *specials, dyn_arr_t *pair_arr, int device, size_t *len,
                                    uint64_t **id_off, uint64_t **byte_off, size_t *ndocs);
 /* bpe_encode_docs and bpe_encode_split_special (specials may be NULL: none) with the device encoder chosen:
- * mode is BPE_ENC_WINDOW (what those two do), BPE_ENC_PIECE or BPE_ENC_AUTO (bpe_gpu.h, bpe_gpu_encode_docs_mode).
+ * mode is BPE_ENC_WINDOW (what those two do), BPE_ENC_PIECE, BPE_ENC_PIECE_LONG or BPE_ENC_AUTO (bpe_gpu.h, bpe_gpu_encode_docs_mode).
  * The ids are the same under every mode; lists beyond the window encoder's limits stay on the device under
  * the other two.  Results and ownership as bpe_encode_docs / bpe_encode_split. */
 uint32_t *bpe_encode_docs_mode(const uint8_t *bytes, size_t n, const uint64_t *doc_off, size_t ndocs, dyn_arr_t *pair_arr,

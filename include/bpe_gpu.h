@@ -77,7 +77,7 @@ typedef struct {
     uint64_t hot_scanned;     /* hot-set entries reduced, summed over the merges */
     uint64_t enc_path;        /* encode: 1 window-local replay, 3 the same after its wide-halo
                                  retry, 2 global batched replay, 4 piece-local replay
-                                 (document batches under BPE_ENC_PIECE / BPE_ENC_AUTO) */
+                                 (document batches under BPE_ENC_PIECE / BPE_ENC_PIECE_LONG / BPE_ENC_AUTO) */
     uint64_t enc_windows;     /* encode: windows replayed (window path)           */
     uint64_t relists;         /* training: byte-pair position lists rebuilt       */
     uint64_t batches;         /* training: merge batches (several merges per scan/apply pair) */
@@ -250,10 +250,14 @@ int bpe_gpu_fetch_doc_offsets(bpe_gpu_ctx *ctx, uint64_t *out, size_t cap, size_
    what bpe_gpu_encode_docs and bpe_gpu_encode_split do.  BPE_ENC_PIECE: the piece-local replay, whose cost
    follows the length of a document and not the list: any valid list whose ids (256 + n_merges) stay within
    bpe_gpu_piece_info's limit, BPE_GPU_ERANGE beyond it; a document longer than a tile takes goes alone through
-   bpe_gpu_encode and is counted in bpe_gpu_docs_info.  BPE_ENC_AUTO: the window encoder when there is a
-   plan, else the piece-local replay, else every document alone.  The ids are the same whichever runs;
-   stats.enc_path tells which did: 1 the windows, 4 the piece-local replay, 2 neither. */
-enum { BPE_ENC_WINDOW = 0, BPE_ENC_PIECE = 1, BPE_ENC_AUTO = 2 };
+   bpe_gpu_encode and is counted in bpe_gpu_docs_info.  BPE_ENC_PIECE_LONG: the piece-local replay with the
+   long-piece kernel behind it: a document longer than a tile takes is replayed by one workgroup, on the same
+   stream and with no host round trip; only a document beyond bpe_gpu_long_piece_info's limit goes alone through
+   bpe_gpu_encode, and bpe_gpu_docs_info counts only those.  The same id limit.  BPE_ENC_AUTO: the window
+   encoder when there is a plan, else BPE_ENC_PIECE_LONG, else every document alone.  The ids are the same
+   whichever runs; stats.enc_path tells which did: 1 the windows, 4 the piece-local replay (with or without the
+   long-piece kernel), 2 neither. */
+enum { BPE_ENC_WINDOW = 0, BPE_ENC_PIECE = 1, BPE_ENC_AUTO = 2, BPE_ENC_PIECE_LONG = 3 };
 int bpe_gpu_encode_docs_mode(bpe_gpu_ctx *ctx, const uint64_t *doc_off, size_t ndocs,
                              const uint32_t *pairs, size_t n_merges, int mode);
 /* The piece-local replay's geometry (no GPU; for the host-side tests):
@@ -263,6 +267,13 @@ int bpe_gpu_piece_info(uint64_t *out4);
 /* out8 = {ndocs, docs through the fallback, windows, windows failed, core, halo,
    tiles of the piece-local replay, the largest number of rounds (merges of one document) any tile ran} */
 int bpe_gpu_docs_info(bpe_gpu_ctx *ctx, uint64_t *out8);
+/* The long-piece kernel's geometry (no GPU): out2 = {positions a workgroup holds, bytes of the longest
+   document it takes} */
+int bpe_gpu_long_piece_info(uint64_t *out2);
+/* Of the last document encode: out4 = {documents the long-piece kernel encoded, documents beyond its limit
+   (left to the fallback), the largest number of rounds of one such document, workgroups launched}; all 0 when
+   that kernel did not run.  BPE_GPU_ESTATE where bpe_gpu_docs_info returns it. */
+int bpe_gpu_long_info(bpe_gpu_ctx *ctx, uint64_t *out4);
 /* bpe_gpu_decode plus byte_off[0..ndocs] (bytes of document d = out[byte_off[d], byte_off[d+1])) */
 int bpe_gpu_decode_docs(bpe_gpu_ctx *ctx, const uint32_t *ids, size_t len, const uint64_t *id_off,
                         size_t ndocs, const uint32_t *pairs, size_t n_merges,

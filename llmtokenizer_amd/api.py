@@ -148,8 +148,8 @@ def _doc_offsets(offsets):
     return np.ascontiguousarray(offsets, dtype=np.uint64).reshape(-1)
 
 
-# bpe_gpu.h BPE_ENC_WINDOW / BPE_ENC_PIECE / BPE_ENC_AUTO: the device encoder of a document batch
-ENCODERS = {"window": 0, "piece": 1, "auto": 2}
+# bpe_gpu.h BPE_ENC_WINDOW / BPE_ENC_PIECE / BPE_ENC_AUTO / BPE_ENC_PIECE_LONG: the device encoder of a document batch
+ENCODERS = {"window": 0, "piece": 1, "auto": 2, "piece_long": 3}
 
 
 def _encoder(name):
@@ -170,13 +170,27 @@ def piece_info():
     return {k: int(out[i]) for i, k in enumerate(PIECE_INFO)}
 
 
+LONG_PIECE_INFO = ("positions", "piece_max")
+
+
+def long_piece_info():
+    """The long-piece kernel's geometry (bpe_gpu_long_piece_info): the positions a workgroup holds and the bytes of
+    the longest document it takes; under "piece_long" / "auto" only longer ones go through the per-document
+    fallback.  No GPU."""
+    out = np.zeros(2, dtype=np.uint64)
+    _lib.check(_lib.load().bpe_gpu_long_piece_info(out.ctypes.data_as(ctypes.c_void_p)), "long_piece_info")
+    return {k: int(out[i]) for i, k in enumerate(LONG_PIECE_INFO)}
+
+
 def encode_batch(docs, merges, device=0, encoder="window"):
     """Encode a batch of documents (bytes-like objects) in one pass: no merge
     crosses a document boundary.  Returns (ids, offsets): ids[offsets[d]:offsets[d + 1]]
     equals encode(docs[d], merges); offsets is uint64 of length len(docs) + 1.
     encoder: "window" (merge lists within the window encoder's limits run on it, others document by
-    document), "piece" (the piece-local replay: any list up to piece_info()["max_ids"] ids) or "auto"
-    (the first that applies); the ids are the same."""
+    document), "piece" (the piece-local replay: any list up to piece_info()["max_ids"] ids; documents beyond
+    piece_info()["piece_max"] bytes go through the fallback), "piece_long" (the same with the long-piece kernel
+    behind it: only documents beyond long_piece_info()["piece_max"] do) or "auto" (the window encoder when the
+    list fits it, else "piece_long"); the ids are the same."""
     L = _lib.load()
     mode = _encoder(encoder)
     docs = [bytes(d) for d in docs]
@@ -1250,7 +1264,8 @@ class Engine:
     def encode_docs(self, offsets, merges, encoder="window"):
         """encode the resident bytes as documents: document d is bytes
         [offsets[d], offsets[d + 1]) (bpe_gpu_encode_docs_mode); then ids(), doc_offsets(), docs_info().
-        encoder: "window", "piece" or "auto", as in api.encode_batch; stats()["enc_path"] tells which ran."""
+        encoder: "window", "piece", "piece_long" or "auto", as in api.encode_batch; stats()["enc_path"] tells
+        which ran."""
         off = _doc_offsets(offsets)
         if off.size < 1:
             raise BpeError("encode_docs: offsets must hold ndocs + 1 entries")
@@ -1371,6 +1386,16 @@ class Engine:
         out = np.zeros(8, dtype=np.uint64)
         _lib.check(self.L.bpe_gpu_docs_info(self.ctx, out.ctypes.data_as(ctypes.c_void_p)), "docs_info")
         return {k: int(out[i]) for i, k in enumerate(self.DOCS_INFO)}
+
+    LONG_INFO = ("long_pieces", "long_fallback", "long_rounds", "workgroups")
+
+    def long_info(self):
+        """the long-piece kernel's counters of the last encode_docs / encode_split (bpe_gpu_long_info): documents
+        it encoded, documents beyond its limit (left to the fallback), the largest round count of one, and the
+        workgroups launched; all 0 when the encoder was not "piece_long" (or "auto" choosing it)"""
+        out = np.zeros(4, dtype=np.uint64)
+        _lib.check(self.L.bpe_gpu_long_info(self.ctx, out.ctypes.data_as(ctypes.c_void_p)), "long_info")
+        return {k: int(out[i]) for i, k in enumerate(self.LONG_INFO)}
 
     def map_ids(self, vocab):
         """rewrite the resident ids of the last encode in place to the ids of vocab (a vocab.Vocab):

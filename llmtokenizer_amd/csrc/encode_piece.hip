@@ -24,7 +24,9 @@
 // at most EP_PIECE_MAX = EP_W - EP_C bytes fits.  A longer piece can only be
 // the last one its tile owns (EP_PIECE_MAX >= EP_C: it ends beyond the core);
 // the tile leaves it out and counts it, and the host sends it through the
-// per-document fallback (engine.hip).  The tile's first piece comes from a
+// per-document fallback (engine.hip); given a list (EncPieceArgs::lng) the
+// tile also appends the piece to it, for k_enc_long (encode_long.hip), and
+// only what that kernel leaves goes to the fallback.  The tile's first piece comes from a
 // lane-parallel search of the resident offsets, 64 probes per round trip.
 //
 // LDS per position: the id (u32) and the cached rank of the pair starting
@@ -72,7 +74,9 @@ static_assert(EP_W / 32 == EP_T, "one bitmap word per lane in the output's prefi
 static_assert(EP_W <= 32 * EP_T, "a lane's range fits one 32-bit mask");
 static_assert(EP_PIECE_MAX >= EP_C, "a piece too long for its tile is the last one the tile owns");
 
-enum { EPC_LONG, EPC_ROUNDS, EPC_ERROR, EPC_WORDS };  // control words (ctl)
+// control words (ctl); the last three are k_enc_long's (encode_long.hip): pieces it took, pieces beyond its limit,
+// the largest round count of a piece
+enum { EPC_LONG, EPC_ROUNDS, EPC_ERROR, EPC_LTAKEN, EPC_LOVER, EPC_LROUNDS, EPC_WORDS };
 
 struct EncPieceArgs {
     const uint8_t *bytes;            // [n] (+ 64 bytes of slack)
@@ -84,8 +88,10 @@ struct EncPieceArgs {
     const unsigned long long *ht;    // a << 42 | b << 21 | rank + 1 (0: empty)
     uint32_t *stage;                 // [n] tile w's ids from its first owned byte on
     uint32_t *cnt;                   // [ndocs + 1] ids per piece (zeroed: empty, long and unowned pieces stay 0)
-    uint32_t *tfirst, *tcnt;         // [tiles] the tile's first piece, its ids
+    uint32_t *tfirst, *tcnt;         // [tiles] the tile's first piece, its ids ([2 * tiles] with lng: a long piece each)
     uint32_t *ctl;                   // [EPC_WORDS] long pieces, largest round count, internal error
+    uint32_t *lng;                   // [tiles] the long pieces left out, in any order (nullptr: only counted)
+    uint32_t tiles;
 };
 
 // the wave's own LDS stores and atomics are done before its next LDS loads
@@ -151,7 +157,10 @@ __global__ __launch_bounds__(EP_T) void k_enc_piece(EncPieceArgs A) {
     const bool lng = R - A.doc_off[i1 - 1] > EP_PIECE_MAX;  // only the last piece can be
     if (lng) {
         R = A.doc_off[i1 - 1];
-        if (lane == 0) atomicAdd(&A.ctl[EPC_LONG], 1u);
+        if (lane == 0) {
+            const uint32_t s = atomicAdd(&A.ctl[EPC_LONG], 1u);  // (at most one a tile: s < tiles)
+            if (A.lng) A.lng[s] = i1 - 1;
+        }
     }
     if (R - L > EP_W) {  // (offsets that do not rise)
         if (lane == 0) atomicOr(&A.ctl[EPC_ERROR], 1u);

@@ -28,6 +28,7 @@
 #include "encode_win.hip"
 #include "encode_docs.hip"
 #include "encode_piece.hip"
+#include "encode_long.hip"
 #include "split.hip"
 #include "split_o200k.hip"
 #include "train_split.hip"
@@ -331,6 +332,7 @@ struct bpe_gpu_ctx {
     uint64_t docs_n = 0;
     uint64_t *d_idoff = nullptr;
     uint64_t docs_info[8] = {};
+    uint64_t long_info[4] = {};  // bpe_gpu_long_info's, of the same encode
     // the last bpe_gpu_split: piece starts + n (device, [split_n + 1]).  A buffer of its own, outside
     // train_allocs and the pool: it outlives the encodes over it and goes with the bytes it describes.
     bool split_ready = false;
@@ -2601,22 +2603,27 @@ EpTable ep_table(const uint32_t *pairs, size_t m, std::vector<uint32_t> &img) {
 
 // Encode c's bytes as documents (d_doc[ndocs + 1] on the device) by the
 // piece-local replay (encode_piece.hip) into c's ids and id offsets, as ed_run
-// leaves them; *nlong = documents longer than EP_PIECE_MAX, which have no ids yet.
-int ep_run(bpe_gpu_ctx *c, const uint32_t *pairs, size_t n_merges, const uint64_t *d_doc, uint64_t ndocs, uint64_t *nlong,
-           uint64_t *tiles_out, uint64_t *rounds) {
+// leaves them; *nlong = documents that have no ids yet: those longer than
+// EP_PIECE_MAX, or, with_long (k_enc_long behind the tiles, encode_long.hip),
+// those longer than EL_PIECE_MAX.  linfo: bpe_gpu_long_info's four words.
+int ep_run(bpe_gpu_ctx *c, const uint32_t *pairs, size_t n_merges, const uint64_t *d_doc, uint64_t ndocs, bool with_long,
+           uint64_t *nlong, uint64_t *tiles_out, uint64_t *rounds, uint64_t *linfo) {
     const uint64_t n = c->n0, tiles = (n + EP_C - 1) / EP_C;
+    const uint64_t entries = with_long ? 2 * tiles : tiles;  // of (tfirst, tcnt): a long piece each behind the tiles'
+    const uint32_t lgrid = with_long ? (uint32_t)std::min<uint64_t>(tiles, EL_GRID) : 0;
     int r;
     const EpTable T = ep_table(pairs, n_merges, c->ew_stage);
     void *d_img;
     if ((r = dscratch(c, DS_EP_TABLES, T.words * 4, &d_img))) return r;
     HIPCHK(hipMemcpyAsync(d_img, c->ew_stage.data(), T.words * 4, hipMemcpyHostToDevice, c->st));
-    uint32_t *ids, *stage, *cnt, *tfirst, *tcnt, *ctl;
+    uint32_t *ids, *stage, *cnt, *tfirst, *tcnt, *ctl, *lng = nullptr;
     uint64_t *d_idoff;
     if ((r = dalloc(c, &ids, std::max<uint64_t>(n, 1), false))) return r;
     if ((r = dalloc(c, &stage, std::max<uint64_t>(n, 1), false))) return r;
     if ((r = dalloc(c, &cnt, ndocs + 1))) return r;  // zeroed
-    if ((r = dalloc(c, &tfirst, std::max<uint64_t>(tiles, 1), false))) return r;
-    if ((r = dalloc(c, &tcnt, std::max<uint64_t>(tiles, 1), false))) return r;
+    if ((r = dalloc(c, &tfirst, std::max<uint64_t>(entries, 1), false))) return r;
+    if ((r = dalloc(c, &tcnt, std::max<uint64_t>(entries, 1), with_long))) return r;  // (zeroed: the unused long entries)
+    if (with_long && (r = dalloc(c, &lng, std::max<uint64_t>(tiles, 1), false))) return r;
     if ((r = dalloc(c, &ctl, EPC_WORDS))) return r;  // zeroed
     if ((r = dalloc(c, &d_idoff, ndocs + 1, false))) return r;
     c->h.ids_out = ids;
@@ -2634,13 +2641,17 @@ int ep_run(bpe_gpu_ctx *c, const uint32_t *pairs, size_t n_merges, const uint64_
     A.tfirst = tfirst;
     A.tcnt = tcnt;
     A.ctl = ctl;
+    A.lng = lng;
+    A.tiles = (uint32_t)tiles;
     if (tiles) k_enc_piece<<<(uint32_t)tiles, EP_T, 0, c->st>>>(A);
+    HIPCHK(hipGetLastError());
+    if (lgrid) k_enc_long<<<lgrid, EL_T, 0, c->st>>>(A);  // (reads the list's length on the device)
     HIPCHK(hipGetLastError());
     r = ROCPRIM_RUN(c, DS_SCAN_TMP, rocprim::exclusive_scan(tmp, tb, cnt, d_idoff, (uint64_t)0, ndocs + 1, rocprim::plus<uint64_t>(), c->st));
     if (r) return r;
     if (tiles)
-        k_ep_gather<<<(uint32_t)((tiles + EPG_T / 64 - 1) / (EPG_T / 64)), EPG_T, 0, c->st>>>(stage, d_doc, d_idoff, tfirst, tcnt,
-                                                                                            tiles, ids);
+        k_ep_gather<<<(uint32_t)((entries + EPG_T / 64 - 1) / (EPG_T / 64)), EPG_T, 0, c->st>>>(stage, d_doc, d_idoff, tfirst, tcnt,
+                                                                                              entries, ids);
     HIPCHK(hipGetLastError());
     uint32_t h[EPC_WORDS] = {};
     uint64_t total = 0;
@@ -2648,9 +2659,14 @@ int ep_run(bpe_gpu_ctx *c, const uint32_t *pairs, size_t n_merges, const uint64_
     HIPCHK(hipMemcpyAsync(&total, d_idoff + ndocs, 8, hipMemcpyDeviceToHost, c->st));
     HIPCHK(hipStreamSynchronize(c->st));
     if (h[EPC_ERROR])
-        return fail(BPE_GPU_EINTERNAL, h[EPC_ERROR] & 2u ? "encode_piece: a tile ran more rounds than it has positions"
-                                                         : "encode_piece: a tile's documents do not fit it");
-    *nlong = h[EPC_LONG];
+        return fail(BPE_GPU_EINTERNAL, h[EPC_ERROR] & 4u   ? "encode_long: a piece ran more rounds than it has positions"
+                                       : h[EPC_ERROR] & 2u ? "encode_piece: a tile ran more rounds than it has positions"
+                                                           : "encode_piece: a tile's documents do not fit it");
+    if (with_long && h[EPC_LTAKEN] + h[EPC_LOVER] != h[EPC_LONG])
+        return fail(BPE_GPU_EINTERNAL, "encode_long: not every listed piece was visited");
+    *nlong = with_long ? h[EPC_LOVER] : h[EPC_LONG];
+    const uint64_t li[4] = {h[EPC_LTAKEN], h[EPC_LOVER], h[EPC_LROUNDS], lgrid};
+    memcpy(linfo, li, sizeof li);
     *tiles_out = tiles;
     *rounds = h[EPC_ROUNDS];
     c->ids_len = total;
@@ -3588,9 +3604,10 @@ int bpe_gpu_docs_window(const uint64_t *doc_off, size_t ndocs, uint64_t n, uint3
 // that read offsets on the host download them, and only they do).
 static int encode_docs_run(bpe_gpu_ctx *c, const uint64_t *doc_off, size_t ndocs, const uint32_t *pairs, size_t n_merges,
                            double t_chk, int mode) {
-    if (mode != BPE_ENC_WINDOW && mode != BPE_ENC_PIECE && mode != BPE_ENC_AUTO) return fail(BPE_GPU_EINVAL, "encode_docs: no such encoder mode");
+    if (mode != BPE_ENC_WINDOW && mode != BPE_ENC_PIECE && mode != BPE_ENC_AUTO && mode != BPE_ENC_PIECE_LONG) return fail(BPE_GPU_EINVAL, "encode_docs: no such encoder mode");
     const bool ep_fits = 256 + (uint64_t)n_merges <= EP_MAX_IDS;
-    if (mode == BPE_ENC_PIECE && !ep_fits) return fail(BPE_GPU_ERANGE, "encode_docs: the merge list's ids exceed the piece-local replay's 2^21");
+    const bool piece_mode = mode == BPE_ENC_PIECE || mode == BPE_ENC_PIECE_LONG;
+    if (piece_mode && !ep_fits) return fail(BPE_GPU_ERANGE, "encode_docs: the merge list's ids exceed the piece-local replay's 2^21");
     const uint64_t n = c->n0;
     const bool resident = doc_off == nullptr;
     std::vector<uint64_t> h_split;
@@ -3613,10 +3630,12 @@ static int encode_docs_run(bpe_gpu_ctx *c, const uint64_t *doc_off, size_t ndocs
     free_train(c);
     // first pass: every window of the concatenated stream (nothing else runs when none fails)
     std::vector<uint8_t> failed;  // documents for the fallback (sized when there are any)
-    uint64_t nfailed = 0, wfailed = 0, nwin = 0, core = 0, halo = 0, tiles = 0, rounds = 0;
+    uint64_t nfailed = 0, wfailed = 0, nwin = 0, core = 0, halo = 0, tiles = 0, rounds = 0, linfo[4] = {};
     bool first_pass = false;
-    const EwPlan P = n && mode != BPE_ENC_PIECE ? ew_plan(pairs, n_merges, c->ew_stage) : EwPlan{};
-    const bool piece = mode == BPE_ENC_PIECE || (mode == BPE_ENC_AUTO && n && !P.ok && ep_fits);
+    const EwPlan P = n && !piece_mode ? ew_plan(pairs, n_merges, c->ew_stage) : EwPlan{};
+    const bool piece = piece_mode || (mode == BPE_ENC_AUTO && n && !P.ok && ep_fits);
+    const bool with_long = piece && mode != BPE_ENC_PIECE;  // k_enc_long takes the pieces the tiles leave out
+    const uint64_t piece_max = with_long ? EL_PIECE_MAX : EP_PIECE_MAX;
     const double t_plan = now_ms();
     // the offsets on the device: the split's, or the caller's uploaded
     const uint64_t *d_doc = c->d_split;
@@ -3651,14 +3670,15 @@ static int encode_docs_run(bpe_gpu_ctx *c, const uint64_t *doc_off, size_t ndocs
                 nfailed += failed[d];
             }
     } else if (piece) {
-        // the piece-local replay: only the documents longer than a tile takes are left for the fallback
-        if ((r = ep_run(c, pairs, n_merges, d_doc, ndocs, &nfailed, &tiles, &rounds))) return r;
+        // the piece-local replay: only the documents longer than a tile (with_long: the long kernel) takes are left
+        // for the fallback
+        if ((r = ep_run(c, pairs, n_merges, d_doc, ndocs, with_long, &nfailed, &tiles, &rounds, linfo))) return r;
         first_pass = true;
         if (nfailed) {
             if ((r = host_offsets())) return r;
             failed.assign(ndocs, 0);
             nfailed = 0;
-            for (size_t d = 0; d < ndocs; d++) nfailed += failed[d] = doc_off[d + 1] - doc_off[d] > EP_PIECE_MAX;
+            for (size_t d = 0; d < ndocs; d++) nfailed += failed[d] = doc_off[d + 1] - doc_off[d] > piece_max;
         }
     } else {
         // no plan (too many merges or layers), or no bytes: every document with bytes goes through the fallback
@@ -3724,12 +3744,13 @@ static int encode_docs_run(bpe_gpu_ctx *c, const uint64_t *doc_off, size_t ndocs
     c->docs_n = ndocs;
     const uint64_t info[8] = {ndocs, nfailed, nwin, wfailed, core, halo, tiles, rounds};
     memcpy(c->docs_info, info, sizeof info);
+    memcpy(c->long_info, linfo, sizeof linfo);
     c->merges_done = 0;
     c->stats.enc_path = piece ? 4 : first_pass ? 1 : 2;
     c->stats.enc_windows = nwin;
     c->stats.n_out = c->ids_len;
     c->stats.merges = n_merges;
-    c->stats.iterations = piece ? rounds : P.nb;
+    c->stats.iterations = piece ? std::max(rounds, linfo[2]) : P.nb;
     c->stats.occurrences = n - c->ids_len;
     c->stats.ms_train = t1 - t0;
     c->stats.ms_total = t1 - t0;
@@ -3765,6 +3786,20 @@ int bpe_gpu_piece_info(uint64_t *out4) {
     out4[1] = EP_C;
     out4[2] = EP_PIECE_MAX;
     out4[3] = EP_MAX_IDS;
+    return 0;
+}
+
+int bpe_gpu_long_piece_info(uint64_t *out2) {
+    if (!out2) return BPE_GPU_EINVAL;
+    out2[0] = EL_W;
+    out2[1] = EL_PIECE_MAX;
+    return 0;
+}
+
+int bpe_gpu_long_info(bpe_gpu_ctx *c, uint64_t *out4) {
+    if (!c || !out4) return BPE_GPU_EINVAL;
+    if (!c->ids_ready || !c->docs_ready) return fail(BPE_GPU_ESTATE, "no document batch: encode_docs first");
+    memcpy(out4, c->long_info, sizeof c->long_info);
     return 0;
 }
 

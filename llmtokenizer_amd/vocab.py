@@ -412,7 +412,7 @@ class Tokenizer:
     """Encode to and decode from a vocabulary's own ids on one GPU: the split of vocab.rule around
     vocab.specials, the merges applied inside the pieces, the ids rewritten on the device.  encoder: "auto"
     (the window encoder for a merge list within its limits, which encodes as before; the piece-local replay
-    for the longer lists of cl100k_base, Llama 3, Qwen2 and o200k_base), "window" or "piece" (api.encode_batch)."""
+    for the longer lists of cl100k_base, Llama 3, Qwen2 and o200k_base), "window", "piece" or "piece_long" (api.encode_batch)."""
 
     def __init__(self, vocab, device=0, encoder="auto"):
         if encoder not in api.ENCODERS:

@@ -11,6 +11,7 @@ timed call ends with the engine's own stream synchronise (it reads the id count 
                             path costs where a plan exists
   noplan_piece              the piece path with the same list padded beyond 65,279 merges by records that never
                             match (byte 1 before the id of the record before)
+  noplan_auto               the same under encoder="auto", which puts the long-piece kernel's launch behind the tiles
   noplan_parent             encoder="window" with the padded list, i.e. the per-document fallback, on the first
                             --fallback-pieces pieces only, scaled per piece (--fallback-repeats runs, none warm:
                             each takes many seconds)
@@ -77,7 +78,8 @@ def main():
         e.encode_split(m, encoder=encoder)
         return (time.perf_counter() - t0) * 1e3
 
-    legs = {"plan_window": (merges, "window"), "plan_piece": (merges, "piece"), "noplan_piece": (padded, "piece")}
+    legs = {"plan_window": (merges, "window"), "plan_piece": (merges, "piece"), "noplan_piece": (padded, "piece"),
+            "noplan_auto": (padded, "auto")}
     sums, info = {}, {}
     for name, (m, enc) in legs.items():  # warm, and checked against each other
         leg(m, enc)
