@@ -63,7 +63,11 @@ COBJ_NORM := $(patsubst $(PKG)/src/%.c,$(BUILD)/%.o,$(CSRC_NORM))
 # which none of the models above has
 CSRC_ENC := $(PKG)/src/bpe_encoder.c
 COBJ_ENC := $(patsubst $(PKG)/src/%.c,$(BUILD)/%.o,$(CSRC_ENC))
-HIPDEPS :=$(wildcard $(PKG)/csrc/*.hip $(PKG)/csrc/*.h) $(PKG)/src/bpe_split_presets.h $(PKG)/src/bpe_o200k_rule.h $(PKG)/src/bpe_nfc_rule.h include/bpe_gpu.h
+# decoded text: src/bpe_utf8.c is host code alone (BPE_TEXT_REPLACE / _HOLD in plain C over src/bpe_utf8_rule.h; no
+# engine call)
+CSRC_UTF8 := $(PKG)/src/bpe_utf8.c
+COBJ_UTF8 := $(patsubst $(PKG)/src/%.c,$(BUILD)/%.o,$(CSRC_UTF8))
+HIPDEPS :=$(wildcard $(PKG)/csrc/*.hip $(PKG)/csrc/*.h) $(PKG)/src/bpe_split_presets.h $(PKG)/src/bpe_o200k_rule.h $(PKG)/src/bpe_nfc_rule.h $(PKG)/src/bpe_utf8_rule.h include/bpe_gpu.h
 
 all: $(PKG)/libbpe_amd.so tools/bpe_main oracle
 
@@ -76,7 +80,7 @@ $(BUILD)/engine.o: $(HIPDEPS) | $(BUILD)
 $(BUILD)/%.o: $(PKG)/src/%.c $(wildcard include/*.h $(PKG)/src/*.h $(PKG)/csrc/unicode_classes.h $(PKG)/csrc/unicode_case_classes.h $(PKG)/csrc/unicode_nfc.h) | $(BUILD)
 	$(CC) $(CFLAGS) -c $< -o $@
 
-$(PKG)/libbpe_amd.so: $(BUILD)/engine.o $(COBJ) $(COBJ_GPU) $(COBJ_TS) $(COBJ_SP) $(COBJ_SPECIAL) $(COBJ_VOCAB) $(COBJ_TEXTS) $(COBJ_SPANS) $(COBJ_STREAM) $(COBJ_WHOLE) $(COBJ_ROWS) $(COBJ_NORM) $(COBJ_ENC)
+$(PKG)/libbpe_amd.so: $(BUILD)/engine.o $(COBJ) $(COBJ_GPU) $(COBJ_TS) $(COBJ_SP) $(COBJ_SPECIAL) $(COBJ_VOCAB) $(COBJ_TEXTS) $(COBJ_SPANS) $(COBJ_STREAM) $(COBJ_WHOLE) $(COBJ_ROWS) $(COBJ_NORM) $(COBJ_ENC) $(COBJ_UTF8)
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^ -lm -ldl -lpthread
 
 tools/bpe_main: tools/bpe_main.c $(PKG)/libbpe_amd.so

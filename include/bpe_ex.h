@@ -246,6 +246,15 @@ int bpe_unpack_rows_host(const void *rows, int cell_bytes, size_t B, uint32_t L,
                          const bpe_gpu_rows *desc, uint32_t *ids, size_t ids_cap, size_t *n, uint64_t *text_off,
                          uint32_t *bounds, char *msg, size_t msg_cap);
 
+/* BPE_TEXT_RAW / _REPLACE / _HOLD (bpe_gpu.h, "Decoded text") in plain C, no GPU: one pass from the left over
+ * src/bpe_utf8_rule.h, the definition the device is held to (src/bpe_utf8.c).  in[0 .. n) holds T texts, text k
+ * being in[byte_off[k] .. byte_off[k + 1]) (the offsets run from 0 to n without falling); byte_off == NULL with T == 0:
+ * one text.  Two-phase as the decoders: *out_len = the length of the result, and with out == NULL nothing else is
+ * written; else out, byte_off_out (T + 1 entries, unless NULL or byte_off is) and held (T entries, or 1 for the one
+ * text, unless NULL).  BPE_GPU_EINVAL for bad offsets, another `errors` and cap < *out_len. */
+int bpe_utf8_repair_host(const uint8_t *in, size_t n, const uint64_t *byte_off, size_t T, int errors, uint8_t *out,
+                         size_t cap, size_t *out_len, uint64_t *byte_off_out, uint32_t *held);
+
 /* statistics of the last compress/compress_ex/bpe_train_bytes/bpe_encode_bytes/bpe_encode_docs/bpe_encode_split(_preset) */
 int bpe_last_stats(bpe_gpu_stats *out);
 

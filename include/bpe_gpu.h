@@ -984,6 +984,71 @@ int bpe_gpu_fetch_bytes(bpe_gpu_ctx *ctx, uint8_t *out, size_t cap, size_t *len)
    them; out may be NULL, *count = T + 1.  BPE_GPU_ESTATE without a text batch. */
 int bpe_gpu_fetch_text_byte_offsets(bpe_gpu_ctx *ctx, uint64_t *out, size_t cap, size_t *count);
 
+/* ------------------------------------------------------------------------
+ * Decoded text: the decoders' bytes made well-formed UTF-8 on the device, so
+ * that a strict str(bytes, "utf-8") of every text cannot fail.  Generation cut
+ * at a token limit ends inside a character, a byte-level vocabulary can emit
+ * any bytes, and a streaming caller decodes a row after every step.
+ *
+ * The contract.  A text is a document of bpe_gpu_decode_text, a row of
+ * bpe_gpu_decode_rows_text, or the one flat sequence.  Its decoded bytes are
+ * what the decoder emits (NULs dropped, specials expanded, as ever), read as
+ * UTF-8 per Unicode Table 3-7: no overlong form, no surrogate, nothing above
+ * U+10FFFF.  `errors` says what becomes of them:
+ *   BPE_TEXT_RAW.  The bytes as the decoders give them; held is all 0.
+ *   BPE_TEXT_REPLACE.  Every well-formed sequence is copied.  Every maximal
+ *     subpart of an ill-formed subsequence (a lead byte C2..F4 and as many
+ *     continuation bytes as are still valid for it and lie inside the text, but
+ *     fewer than it needs) becomes EF BF BD (U+FFFD), and so does every other
+ *     byte in no well-formed sequence: a stray 80..BF, C0, C1, F5..FF.  This is
+ *     CPython's bytes.decode("utf-8", "replace").encode("utf-8").
+ *   BPE_TEXT_HOLD.  As REPLACE, but a maximal subpart that ended only because
+ *     the text did (a proper prefix of a well-formed sequence, 1 .. 3 bytes, no
+ *     offending byte behind it) is neither emitted nor replaced: held[k] is its
+ *     length, 0 for every other text.  This is CPython's incremental decoder,
+ *     codecs.getincrementaldecoder("utf-8")("replace"): the text is
+ *     .decode(b, final=False), held[k] the bytes in .getstate()[0].  A streaming
+ *     caller shows the text and decodes the held ids again with the next step's.
+ *     CPython's one exception is kept with it: a text that ends ED A0..BF (a
+ *     truncated surrogate) holds those 2 bytes too, though nothing well-formed
+ *     begins with them; with the next byte behind them both are replaced.
+ *   Texts stay separate.  No sequence reaches from one text into the next: a
+ *     lead byte at the end of text k and a continuation byte at the start of
+ *     text k + 1 are two ill-formed units (or a held tail and a stray byte),
+ *     never one character.  An empty text stays empty, held 0.
+ *   Locality.  A byte's fate depends on b[i - 3 .. i + 3] and the text's bounds
+ *     alone.  A lead byte always begins a unit.  A continuation byte is covered
+ *     exactly when the nearest non-continuation byte within 3 bytes before it,
+ *     inside the same text, is a lead whose valid prefix reaches it.  There is no
+ *     left-to-right dependence beyond that, which is what lets every lane of
+ *     utf8.hip judge its 16 bytes alone.  bpe_ex.h bpe_utf8_repair_host is this
+ *     contract in plain C (src/bpe_utf8_rule.h: the rule both run).
+ *   Length.  The result is at most 3 times the decoded bytes.
+ *   State.  None is kept: the existing decoders, the last unpack's rows and the
+ *     resident ids are untouched, and a context that never asks for a mode
+ *     launches what it always launched (RAW launches no kernel of utf8.hip).
+ *     BPE_GPU_EINVAL for another `errors` value.
+ * ---------------------------------------------------------------------- */
+#define BPE_TEXT_RAW 0
+#define BPE_TEXT_REPLACE 1
+#define BPE_TEXT_HOLD 2
+/* bpe_gpu_decode_docs_vocab / _special / bpe_gpu_decode_docs (vocab, specials NULL or not) followed by `errors`
+   on the device.  id_off == NULL with ndocs == 0: one flat sequence, one text; byte_off is not written then and
+   held has one entry.  byte_off (ndocs + 1 entries, offsets into out) and held (ndocs entries) may each be NULL.
+   Two-phase as the decoders: out == NULL reports *out_len alone. */
+int bpe_gpu_decode_text(bpe_gpu_ctx *ctx, const uint32_t *ids, size_t len, const uint64_t *id_off, size_t ndocs,
+                        const uint32_t *pairs, size_t n_merges, const bpe_gpu_specials *specials,
+                        const bpe_gpu_vocab *vocab, int errors, uint8_t *out, size_t cap, size_t *out_len,
+                        uint64_t *byte_off, uint32_t *held);
+/* bpe_gpu_decode_rows followed by `errors` on the device: byte_off B + 1 entries, held B entries, each may be NULL */
+int bpe_gpu_decode_rows_text(bpe_gpu_ctx *ctx, const uint32_t *pairs, size_t n_merges, const bpe_gpu_specials *specials,
+                             const bpe_gpu_vocab *vocab, int errors, uint8_t *out, size_t cap, size_t *out_len,
+                             uint64_t *byte_off, uint32_t *held);
+/* out4 = {bytes a lane of the repairing kernels takes, bytes per workgroup step (tile), output bytes of a tile that
+   are staged in LDS (a tile worth more is stored directly), workgroups at most (tiles past them: grid strides)}
+   (pure function, no GPU; for the tests) */
+int bpe_gpu_utf8_info(uint64_t *out4);
+
 int bpe_gpu_get_stats(bpe_gpu_ctx *ctx, bpe_gpu_stats *st);
 
 /* Position-keyed checksum of the ids of the last train / encode, computed in

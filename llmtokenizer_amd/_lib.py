@@ -71,6 +71,8 @@ EXPORTS = [
     # bpe_gpu.h / bpe_ex.h: normalization
     "bpe_gpu_normalize", "bpe_gpu_normalize_info", "bpe_gpu_fetch_bytes", "bpe_gpu_fetch_text_byte_offsets",
     "bpe_nfc_host", "bpe_nfc_info",
+    # bpe_gpu.h / bpe_ex.h: decoded text
+    "bpe_gpu_decode_text", "bpe_gpu_decode_rows_text", "bpe_gpu_utf8_info", "bpe_utf8_repair_host",
 ]
 
 
@@ -348,6 +350,10 @@ def load():
     L.bpe_gpu_fetch_text_byte_offsets.argtypes = [vp, vp, sz, ctypes.POINTER(sz)]
     L.bpe_nfc_host.argtypes = [vp, sz, vp, sz, ctypes.POINTER(sz)]
     L.bpe_nfc_info.argtypes = [ctypes.POINTER(ctypes.c_char_p), ctypes.POINTER(ctypes.c_uint64)]
+    L.bpe_gpu_decode_text.argtypes = [vp, vp, sz, vp, sz, vp, sz, spp, vop, ctypes.c_int, vp, sz, ctypes.POINTER(sz), vp, vp]
+    L.bpe_gpu_decode_rows_text.argtypes = [vp, vp, sz, spp, vop, ctypes.c_int, vp, sz, ctypes.POINTER(sz), vp, vp]
+    L.bpe_gpu_utf8_info.argtypes = [vp]
+    L.bpe_utf8_repair_host.argtypes = [vp, sz, vp, sz, ctypes.c_int, vp, sz, ctypes.POINTER(sz), vp, vp]
     L.bpe_release_engines.argtypes = []
     L.bpe_release_engines.restype = None
     _LIB = L

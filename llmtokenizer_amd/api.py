@@ -383,6 +383,45 @@ def normalize_info():
             "lane_bound": int(out[3])}
 
 
+TEXT_ERRORS = {None: 0, "replace": 1, "hold": 2}  # bpe_gpu.h BPE_TEXT_RAW, _REPLACE, _HOLD
+
+
+def _text_errors(errors, what):
+    if errors not in TEXT_ERRORS:
+        raise BpeError(f"{what}: errors must be None, 'replace' or 'hold', not {errors!r}")
+    return TEXT_ERRORS[errors]
+
+
+def utf8_repair_host(data: bytes, byte_off=None, errors="replace"):
+    """(bytes, byte offsets or None, held uint32[T]) of `data` held as T texts by byte_off (None: one text), made
+    well-formed UTF-8 on the host in plain C (bpe_ex.h bpe_utf8_repair_host): the definition the decoders' errors=
+    modes are held to.  No GPU."""
+    L = _lib.load()
+    buf = np.frombuffer(data, dtype=np.uint8)
+    off = None if byte_off is None else np.ascontiguousarray(byte_off, dtype=np.uint64).reshape(-1)
+    if off is not None and off.size < 1:
+        raise BpeError("utf8_repair_host: byte_off must hold T + 1 entries")
+    T = 0 if off is None else off.size - 1
+    vp = ctypes.c_void_p
+    n = ctypes.c_size_t(0)
+    args = (buf.ctypes.data_as(vp), buf.size, None if off is None else off.ctypes.data_as(vp), T, _text_errors(errors, "utf8_repair_host"))
+    _lib.check(L.bpe_utf8_repair_host(*args, None, 0, ctypes.byref(n), None, None), "utf8_repair_host")
+    out = np.zeros(max(n.value, 1), dtype=np.uint8)
+    bo = None if off is None else np.zeros(T + 1, dtype=np.uint64)
+    held = np.zeros(max(T, 1) if off is None else T, dtype=np.uint32)
+    _lib.check(L.bpe_utf8_repair_host(*args, out.ctypes.data_as(vp), out.size, ctypes.byref(n),
+                                      None if bo is None else bo.ctypes.data_as(vp), held.ctypes.data_as(vp)), "utf8_repair_host")
+    return out[:n.value].tobytes(), bo, held
+
+
+def utf8_info():
+    """{"thread", "tile", "stage", "grid"}: bytes a lane of the repairing kernels takes, bytes per workgroup step,
+    output bytes of a tile that are staged in LDS, and workgroups at most (bpe_gpu_utf8_info; for the tests)"""
+    out = np.zeros(4, dtype=np.uint64)
+    _lib.check(_lib.load().bpe_gpu_utf8_info(out.ctypes.data_as(ctypes.c_void_p)), "utf8_info")
+    return {"thread": int(out[0]), "tile": int(out[1]), "stage": int(out[2]), "grid": int(out[3])}
+
+
 def split_info():
     """{"tile", "grid_bytes"}: bytes one workgroup of the split kernels handles per
     step and bytes one grid step covers (bpe_gpu_split_info; for the tests)"""
@@ -1215,10 +1254,11 @@ class Engine:
                                              B.value, ctypes.byref(B)), "fetch_rows")
         return ids, text_off, bounds
 
-    def decode_rows(self, merges, specials=None, vocab=None):
+    def decode_rows(self, merges, specials=None, vocab=None, errors=None):
         """(bytes, byte offsets) of the last unpack_rows(), row k's text being bytes[off[k]:off[k + 1]]
         (bpe_gpu_decode_rows): what decode_docs(ids, text_off, merges, specials, vocab) of the unpacked ids gives,
-        without the ids leaving the device.  The unpacked ids stay and can be decoded again."""
+        without the ids leaving the device.  The unpacked ids stay and can be decoded again.  errors: as decode_docs
+        takes it (bpe_gpu_decode_rows_text)."""
         m = np.ascontiguousarray(merges, dtype=np.uint32).reshape(-1)
         vp = ctypes.c_void_p
         sp = cv = None
@@ -1229,6 +1269,10 @@ class Engine:
             cv = vocab.c_vocab()
         B, n = ctypes.c_size_t(0), ctypes.c_size_t(0)
         args = (self.ctx, m.ctypes.data_as(vp), m.size // 2, sp.ref if sp else None, cv.ref if cv else None)
+        if errors is not None:
+            _lib.check(self.L.bpe_gpu_fetch_rows(self.ctx, None, 0, None, None, None, 0, ctypes.byref(B)), "fetch_rows")
+            return self._decode_text(self.L.bpe_gpu_decode_rows_text, args + (_text_errors(errors, "decode_rows"),), B.value,
+                                     "decode_rows")
         _lib.check(self.L.bpe_gpu_decode_rows(*args, None, 0, ctypes.byref(n), None), "decode_rows")
         _lib.check(self.L.bpe_gpu_fetch_rows(self.ctx, None, 0, None, None, None, 0, ctypes.byref(B)), "fetch_rows")
         out = np.zeros(max(n.value, 1), dtype=np.uint8)
@@ -1403,10 +1447,25 @@ class Engine:
         (bpe_gpu_map_ids).  A second map_ids, or one without ids, raises BpeError (BPE_GPU_ESTATE)."""
         _lib.check(self.L.bpe_gpu_map_ids(self.ctx, vocab.c_vocab().ref), "map_ids")
 
-    def decode_docs(self, ids, offsets, merges, specials=None, vocab=None):
+    def _decode_text(self, fn, args, T, what):
+        """(bytes, byte offsets, held) of one of the _text entry points over T texts: the two phases"""
+        vp = ctypes.c_void_p
+        n = ctypes.c_size_t(0)
+        _lib.check(fn(*args, None, 0, ctypes.byref(n), None, None), what)
+        out = np.zeros(max(n.value, 1), dtype=np.uint8)
+        bo = np.zeros(T + 1, dtype=np.uint64)
+        held = np.zeros(T, dtype=np.uint32)
+        _lib.check(fn(*args, out.ctypes.data_as(vp), out.size, ctypes.byref(n), bo.ctypes.data_as(vp), held.ctypes.data_as(vp)), what)
+        return out[: n.value].tobytes(), bo, held
+
+    def decode_docs(self, ids, offsets, merges, specials=None, vocab=None, errors=None):
         """(bytes, byte offsets) of ids held as documents (bpe_gpu_decode_docs); with specials (see split) the
         id 256 + len(merges) + j is specials[j] (bpe_gpu_decode_docs_special); with vocab (a vocab.Vocab
-        over the same merges and specials) the ids are the vocabulary's (bpe_gpu_decode_docs_vocab)"""
+        over the same merges and specials) the ids are the vocabulary's (bpe_gpu_decode_docs_vocab).  errors:
+        "replace" or "hold" makes every document well-formed UTF-8 on the device (bpe_gpu.h, "Decoded text";
+        bpe_gpu_decode_text) and returns (bytes, byte offsets, held uint32[ndocs]): "replace" as
+        bytes.decode("utf-8", "replace") would, "hold" the same but for an unfinished character at a document's
+        end, whose held[k] bytes are left out."""
         ids = np.ascontiguousarray(ids, dtype=np.uint32)
         off = _doc_offsets(offsets)
         if off.size < 1:
@@ -1425,6 +1484,9 @@ class Engine:
             cv = vocab.c_vocab()
             fn = self.L.bpe_gpu_decode_docs_vocab
             args = (args if specials is not None else args + (None,)) + (cv.ref,)
+        if errors is not None:
+            args = args + (None,) * (9 - len(args)) + (_text_errors(errors, "decode_docs"),)
+            return self._decode_text(self.L.bpe_gpu_decode_text, args, off.size - 1, "decode_docs")
         _lib.check(fn(*args, None, 0, ctypes.byref(n), None), "decode_docs")
         out = np.zeros(max(n.value, 1), dtype=np.uint8)
         bo = np.zeros(off.size, dtype=np.uint64)

@@ -40,6 +40,7 @@
 #include "whole.hip"
 #include "rows.hip"
 #include "normalize.hip"
+#include "utf8.hip"
 
 // (bpe_ex.h, src/bpe_texts.c: the host definition of a text batch's offsets and its resident bytes)
 extern "C" int bpe_texts_check(const uint64_t *text_off, size_t T, size_t n, char *msg, size_t msg_cap);
@@ -3222,11 +3223,14 @@ static uint32_t vm_grid(uint64_t len) {
 // decode_core is the whole of it but for where the ids come from: `ids_from` says whether `ids` is host memory
 // (decode_run: the upload) or lies on the device already (bpe_gpu_decode_rows); either way they are copied into
 // scratch slot DS_DEC_IDS at the same place in the stream's order, since k_ids_unmap rewrites them in place.
+// With d_text (the _text entry points) the bytes are expanded whatever `out` is and stay on the device: *d_text =
+// where they lie (nullptr when there are none), *out_len their number, and `out` and `cap` are not looked at.
 static int decode_core(bpe_gpu_ctx *c, const uint32_t *ids, hipMemcpyKind ids_from, size_t len, const uint32_t *pairs,
                        size_t n_merges, const bpe_gpu_specials *sp, uint8_t *out, size_t cap, size_t *out_len,
-                       const bpe_gpu_vocab *vocab) {
+                       const bpe_gpu_vocab *vocab, uint8_t **d_text = nullptr) {
     if (!c || !out_len || (!ids && len) || (!pairs && n_merges)) return BPE_GPU_EINVAL;
     if (n_merges > 0xFFFFFEFFull) return fail(BPE_GPU_ERANGE, "merge list too long");
+    if (d_text) *d_text = nullptr;
     const uint32_t S = sp ? (uint32_t)sp->count : 0u;
     if (S && n_merges + 256 + S > 0xFFFFFFFFull) return fail(BPE_GPU_ERANGE, "merge list too long for the specials' ids");
     HIPCHK(hipSetDevice(c->dev));
@@ -3297,14 +3301,20 @@ static int decode_core(bpe_gpu_ctx *c, const uint32_t *ids, hipMemcpyKind ids_fr
     if (err[0] & 1) return fail(BPE_GPU_EDATA, "unknown token id");
     if (err[0] & 2) return fail(BPE_GPU_EDATA, "a token's merge record names an unknown id or is cyclic");
     *out_len = total;
-    if (!out) return 0;
-    if (cap < total) return fail(BPE_GPU_EINVAL, "decode: output buffer too small");
+    if (!d_text) {
+        if (!out) return 0;
+        if (cap < total) return fail(BPE_GPU_EINVAL, "decode: output buffer too small");
+    }
     if (len == 0 || total == 0) return 0;
     uint8_t *d_out;
-    if ((r = dscratch(c, DS_DEC_OUT, total, &d_out))) return r;
+    if ((r = dscratch(c, DS_DEC_OUT, total + 16, &d_out))) return r;  // (utf8.hip's 16-byte loads end past the last byte)
     if (S) k_sp_dec_expand<<<1024, 256, 0, c->st>>>(d_ids, len, d_pairs, d_elen, d_off, V0, d_sp, d_soff, d_out);
     else k_dec_expand<<<1024, 256, 0, c->st>>>(d_ids, len, d_pairs, d_elen, d_off, d_out);
     HIPCHK(hipGetLastError());
+    if (d_text) {  // the bytes stay where they lie, for the stream's next kernel
+        *d_text = d_out;
+        return 0;
+    }
     HIPCHK(hipMemcpyAsync(out, d_out, total, hipMemcpyDeviceToHost, c->st));
     HIPCHK(hipStreamSynchronize(c->st));
     return 0;
@@ -4698,6 +4708,145 @@ int bpe_gpu_normalize(bpe_gpu_ctx *c, int form, size_t *n_out) {
     HIPCHK(hipStreamSynchronize(c->st));
     if (n_out) *n_out = (size_t)total;
     return 0;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------ decoded text (utf8.hip; the definition: src/bpe_utf8.c)
+
+// `errors` (U8_REPLACE or U8_HOLD) over the n decoded bytes at d_in (decode_core left them there, with 16 bytes of
+// room behind them), with `batch` held as T texts by the device offsets d_boff, else one text (T == 0).  Two-phase
+// as the decoders.
+static int text_run(bpe_gpu_ctx *c, const uint8_t *d_in, uint64_t n, const uint64_t *d_boff, bool batch, size_t T, int errors,
+                    uint8_t *out, size_t cap, size_t *out_len, uint64_t *byte_off, uint32_t *held) {
+    const size_t texts = batch ? T : 1;
+    if (!batch) byte_off = nullptr;
+    *out_len = 0;
+    if (!n) {  // (nothing decoded: d_boff does not exist)
+        if (out && byte_off) memset(byte_off, 0, (T + 1) * 8);
+        if (out && held) memset(held, 0, texts * 4);
+        return 0;
+    }
+    const uint64_t ntiles = (n + NF_TILE - 1) / NF_TILE;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(ntiles, NF_GRID);
+    int r;
+    unsigned long long *d_cnt, *d_off, total = 0;
+    uint32_t *d_pre;
+    if ((r = dscratch(c, DS_U8_CNT, (ntiles + 1) * 8, &d_cnt)) || (r = dscratch(c, DS_U8_OFF, (ntiles + 1) * 8, &d_off)) ||
+        (r = dscratch(c, DS_U8_PRE, (size_t)ntiles * NF_T * 4, &d_pre)))
+        return r;
+    U8Args A{d_in, n, d_boff, (uint64_t)T, errors};
+    HIPCHK(hipMemsetAsync(d_cnt + ntiles, 0, 8, c->st));
+    k_u8_measure<<<grid, NF_T, 0, c->st>>>(A, d_cnt, d_pre);
+    HIPCHK(hipGetLastError());
+    if ((r = ROCPRIM_RUN(c, DS_U8_TMP, rocprim::exclusive_scan(tmp, tb, d_cnt, d_off, 0ull, (size_t)ntiles + 1, rocprim::plus<unsigned long long>(), c->st))))
+        return r;
+    HIPCHK(hipMemcpyAsync(&total, d_off + ntiles, 8, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipStreamSynchronize(c->st));
+    *out_len = (size_t)total;
+    if (!out) return 0;
+    if (cap < total) return fail(BPE_GPU_EINVAL, "decode_text: output buffer too small");
+    uint8_t *d_new;
+    uint64_t *d_bo = nullptr;
+    uint32_t *d_held = nullptr;
+    if ((r = dscratch(c, DS_U8_OUT, (size_t)total + 16, &d_new))) return r;
+    if (byte_off && (r = dscratch(c, DS_U8_BOFF, (T + 1) * 8, &d_bo))) return r;
+    if (held && (r = dscratch(c, DS_U8_HELD, texts * 4, &d_held))) return r;
+    k_u8_write<<<grid, NF_T, 0, c->st>>>(A, d_off, d_pre, d_new, total);
+    if (d_bo || d_held) k_u8_texts<<<(uint32_t)((T + 256) / 256), 256, 0, c->st>>>(A, d_off, d_pre, d_bo, d_held);
+    HIPCHK(hipGetLastError());
+    if (total && (r = d2h_staged(c, out, d_new, (size_t)total))) return r;
+    if (d_bo) HIPCHK(hipMemcpyAsync(byte_off, d_bo, (T + 1) * 8, hipMemcpyDeviceToHost, c->st));
+    if (d_held) HIPCHK(hipMemcpyAsync(held, d_held, texts * 4, hipMemcpyDeviceToHost, c->st));
+    HIPCHK(hipStreamSynchronize(c->st));
+    return 0;
+}
+
+extern "C" {
+
+int bpe_gpu_utf8_info(uint64_t *out4) {
+    if (!out4) return BPE_GPU_EINVAL;
+    out4[0] = NF_PER;
+    out4[1] = NF_TILE;
+    out4[2] = NF_STAGE;
+    out4[3] = NF_GRID;
+    return 0;
+}
+
+int bpe_gpu_decode_text(bpe_gpu_ctx *c, const uint32_t *ids, size_t len, const uint64_t *id_off, size_t ndocs,
+                        const uint32_t *pairs, size_t n_merges, const bpe_gpu_specials *specials, const bpe_gpu_vocab *vocab,
+                        int errors, uint8_t *out, size_t cap, size_t *out_len, uint64_t *byte_off, uint32_t *held) {
+    if (!c || !out_len || (!ids && len) || (!pairs && n_merges)) return BPE_GPU_EINVAL;
+    if (errors != BPE_TEXT_RAW && errors != BPE_TEXT_REPLACE && errors != BPE_TEXT_HOLD)
+        return fail(BPE_GPU_EINVAL, "decode_text: unknown errors mode (BPE_TEXT_RAW, _REPLACE, _HOLD)");
+    if (!id_off && ndocs) return fail(BPE_GPU_EINVAL, "decode_text: documents without offsets");
+    int r;
+    if (errors == BPE_TEXT_RAW) {  // the decoders as they are
+        if (vocab) r = bpe_gpu_decode_docs_vocab(c, ids, len, id_off, ndocs, pairs, n_merges, specials, vocab, out, cap, out_len, byte_off);
+        else if (specials) r = bpe_gpu_decode_docs_special(c, ids, len, id_off, ndocs, pairs, n_merges, specials, out, cap, out_len, byte_off);
+        else if (id_off) r = bpe_gpu_decode_docs(c, ids, len, id_off, ndocs, pairs, n_merges, out, cap, out_len, byte_off);
+        else r = bpe_gpu_decode(c, ids, len, pairs, n_merges, out, cap, out_len);
+        if (!r && out && held) memset(held, 0, (id_off ? ndocs : 1) * 4);
+        return r;
+    }
+    char msg[400];
+    if (specials && bpe_specials_check(specials, msg, sizeof msg)) return fail(BPE_GPU_EINVAL, msg);
+    if (vocab) {  // (as bpe_gpu_decode_docs_vocab)
+        if ((r = bpe_vocab_check(vocab, pairs, n_merges, msg, sizeof msg))) return fail(r, r == BPE_GPU_EINVAL ? msg : "decode_text: out of memory");
+        if ((specials ? specials->count : 0) != vocab->n_specials)
+            return fail(BPE_GPU_EINVAL, "decode_text: the vocabulary's special count is not the set's");
+    }
+    if (id_off) {  // (as decode_docs_run)
+        if (id_off[0] != 0 || id_off[ndocs] != len) return fail(BPE_GPU_EINVAL, "decode_text: offsets must run from 0 to len");
+        for (size_t d = 0; d < ndocs; d++)
+            if (id_off[d] > id_off[d + 1]) return fail(BPE_GPU_EINVAL, "decode_text: offsets decrease");
+    }
+    uint8_t *d_text;
+    size_t n = 0;
+    if ((r = decode_core(c, ids, hipMemcpyHostToDevice, len, pairs, n_merges, specials, nullptr, 0, &n, vocab, &d_text))) return r;
+    uint64_t *d_idx, *d_boff = nullptr;
+    if (id_off && n) {  // the texts' bounds among the decoded bytes, picked on the device as decode_docs_run picks them
+        if ((r = dscratch(c, DS_DD_IDOFF, (ndocs + 1) * 8, &d_idx)) || (r = dscratch(c, DS_DD_BYTEOFF, (ndocs + 1) * 8, &d_boff))) return r;
+        HIPCHK(hipMemcpyAsync(d_idx, id_off, (ndocs + 1) * 8, hipMemcpyHostToDevice, c->st));
+        k_ed_pick<<<(uint32_t)((ndocs + 256) / 256), 256, 0, c->st>>>((const uint64_t *)c->dscr[DS_DEC_OFF], d_idx, ndocs + 1, d_boff);
+        HIPCHK(hipGetLastError());
+    }
+    return text_run(c, d_text, n, d_boff, id_off != nullptr, ndocs, errors, out, cap, out_len, byte_off, held);
+}
+
+int bpe_gpu_decode_rows_text(bpe_gpu_ctx *c, const uint32_t *pairs, size_t n_merges, const bpe_gpu_specials *specials,
+                             const bpe_gpu_vocab *vocab, int errors, uint8_t *out, size_t cap, size_t *out_len,
+                             uint64_t *byte_off, uint32_t *held) {
+    if (!c || !out_len || (!pairs && n_merges)) return BPE_GPU_EINVAL;
+    if (errors != BPE_TEXT_RAW && errors != BPE_TEXT_REPLACE && errors != BPE_TEXT_HOLD)
+        return fail(BPE_GPU_EINVAL, "decode_rows_text: unknown errors mode (BPE_TEXT_RAW, _REPLACE, _HOLD)");
+    if (!c->rows_ready) return fail(BPE_GPU_ESTATE, "decode_rows_text: no rows: bpe_gpu_unpack_rows first");
+    const size_t len = (size_t)c->rows_n, B = (size_t)c->rows_B;
+    int r;
+    if (errors == BPE_TEXT_RAW) {  // the decoder as it is
+        r = bpe_gpu_decode_rows(c, pairs, n_merges, specials, vocab, out, cap, out_len, byte_off);
+        if (!r && out && held) memset(held, 0, B * 4);
+        return r;
+    }
+    char msg[400];
+    if (specials && bpe_specials_check(specials, msg, sizeof msg)) return fail(BPE_GPU_EINVAL, msg);
+    if (vocab) {  // (as bpe_gpu_decode_docs_vocab)
+        if ((r = bpe_vocab_check(vocab, pairs, n_merges, msg, sizeof msg))) return fail(r, r == BPE_GPU_EINVAL ? msg : "decode_rows_text: out of memory");
+        if ((specials ? specials->count : 0) != vocab->n_specials)
+            return fail(BPE_GPU_EINVAL, "decode_rows_text: the vocabulary's special count is not the set's");
+    }
+    uint8_t *d_text;
+    size_t n = 0;
+    if ((r = decode_core(c, (const uint32_t *)c->dscr[DS_ROWS_IDS], hipMemcpyDeviceToDevice, len, pairs, n_merges, specials, nullptr, 0,
+                         &n, vocab, &d_text)))
+        return r;
+    uint64_t *d_boff = nullptr;
+    if (n) {
+        if ((r = dscratch(c, DS_DD_BYTEOFF, (B + 1) * 8, &d_boff))) return r;
+        k_ed_pick<<<(uint32_t)((B + 256) / 256), 256, 0, c->st>>>((const uint64_t *)c->dscr[DS_DEC_OFF], (const uint64_t *)c->dscr[DS_ROWS_OFF], B + 1, d_boff);
+        HIPCHK(hipGetLastError());
+    }
+    return text_run(c, d_text, n, d_boff, true, B, errors, out, cap, out_len, byte_off, held);
 }
 
 }  // extern "C"

@@ -706,6 +706,13 @@ enum DScr {
     DS_NF_WS,            // ... and the entries it orders and composes
     DS_NF_BOFF,          // bpe_gpu_normalize: a text batch's new byte offsets, copied to DS_TX_BOFF at the end
     DS_EP_TABLES,        // ep_run: the piece-local replay's rank tables (EpTable's image)
+    DS_U8_CNT,           // text_run: the worth of every tile of decoded bytes in output bytes [tiles + 1]
+    DS_U8_OFF,           // ... and their scan, the tiles' output offsets
+    DS_U8_TMP,           // text_run: rocprim temporary of that scan
+    DS_U8_PRE,           // text_run: the worth of a tile's chunks before each 16-byte chunk [tiles * 256]
+    DS_U8_OUT,           // text_run: the repaired bytes
+    DS_U8_BOFF,          // text_run: the texts' offsets into them [T + 1]
+    DS_U8_HELD,          // text_run: the texts' held counts [T]
     DS_COUNT
 };
 // bpe_gpu_train_split takes its eight token-sized arrays as one run of slots

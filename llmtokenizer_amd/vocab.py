@@ -599,7 +599,7 @@ class Tokenizer:
                             out=(new(), new() if return_segments else None, new() if return_positions else None))
         return tuple(t for t in out if t is not None) + (N,)
 
-    def decode_rows(self, rows, lens=None, pad_id=None, eos=None, skip_specials=False, return_bounds=False):
+    def decode_rows(self, rows, lens=None, pad_id=None, eos=None, skip_specials=False, return_bounds=False, errors=None):
         """The texts of a [B, L] grid of ids as a model hands it back: a list of B bytes objects (NUL bytes dropped, as
         decode does).  rows: a 2-D numpy array of uint32, int32, int64 or uint64, or a torch tensor of int32 or int64
         on the tokenizer's device with stride(1) == 1 and stride(0) >= shape[1], such as out[:, P:] of what generate
@@ -611,7 +611,11 @@ class Tokenizer:
         one of vocab.specials (str or bytes), or a list of up to 8 of them.  skip_specials: the ids of vocab.specials
         are left out of the text.  A cell outside the text is never judged, whatever it holds; an id inside it that
         the vocabulary does not hold raises BpeError.  return_bounds: also bounds uint32[B, 2], every row's (start,
-        end) in cells: end - start is the length of what the row generated."""
+        end) in cells: end - start is the length of what the row generated.  errors: None returns bytes as they
+        decode; "replace" returns str, every row made well-formed UTF-8 on the device as bytes.decode("utf-8",
+        "replace") would make it (bpe_gpu.h, "Decoded text"); "hold" the same but for a character left unfinished at a
+        row's end, which is left out, and returns (texts, held): held uint32[B], the bytes of each row kept back, as
+        a streaming caller needs them (with return_bounds: (texts, held, bounds))."""
         many = isinstance(eos, (list, tuple)) or (isinstance(eos, np.ndarray) and eos.ndim)
         stops = [self._special_id(t, "eos", "decode_rows") for t in (eos if many else [eos]) if t is not None]
         if hasattr(rows, "data_ptr"):  # a torch tensor
@@ -621,22 +625,35 @@ class Tokenizer:
                                "call into llmtokenizer_amd, so that both share one HIP runtime")
         e, v = self._eng(), self.vocab
         B, _ = e._unpack_rows(rows, lens, pad_id, stops, v.special_ids if skip_specials else None)
-        out, bo = e.decode_rows(v.merges, v.specials or None, vocab=v)
-        texts = [out[int(bo[k]):int(bo[k + 1])] for k in range(B)]
-        return (texts, e.fetch_rows()[2]) if return_bounds else texts
+        res = self._texts(e.decode_rows(v.merges, v.specials or None, vocab=v, errors=errors), B, errors)
+        return res + (e.fetch_rows()[2],) if return_bounds else res[0] if len(res) == 1 else res
 
-    def decode_batch(self, ids, text_off):
-        """the inverse of encode_batch(texts): the list of the texts' bytes (NUL bytes dropped, as decode does)"""
+    @staticmethod
+    def _texts(dec, T, errors):
+        """(texts,) of a decoder's (bytes, offsets): bytes objects; of (bytes, offsets, held) under errors=: str, made
+        by a strict str(bytes, "utf-8") that the device's repair leaves nothing to refuse, and with "hold" (texts, held)"""
+        out, bo = dec[0], dec[1]
+        texts = [out[int(bo[k]):int(bo[k + 1])] for k in range(T)]
+        if errors is None:
+            return (texts,)
+        texts = [str(t, "utf-8") for t in texts]
+        return (texts, dec[2]) if errors == "hold" else (texts,)
+
+    def decode_batch(self, ids, text_off, errors=None):
+        """the inverse of encode_batch(texts): the list of the texts' bytes (NUL bytes dropped, as decode does).
+        errors: "replace" or "hold" returns str instead, repaired on the device as decode_rows describes; with "hold"
+        (texts, held)."""
         ids = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
         off = np.ascontiguousarray(text_off, dtype=np.uint64).reshape(-1)
         v = self.vocab
-        out, bo = self._eng().decode_docs(ids, off, v.merges, v.specials or None, vocab=v)
-        return [out[int(bo[k]):int(bo[k + 1])] for k in range(off.size - 1)]
+        res = self._texts(self._eng().decode_docs(ids, off, v.merges, v.specials or None, vocab=v, errors=errors), off.size - 1, errors)
+        return res[0] if len(res) == 1 else res
 
-    def decode(self, ids):
+    def decode(self, ids, errors=None):
         """the bytes of vocabulary ids (NUL bytes dropped, as api.decode_batch does); an id the vocabulary does
-        not hold raises BpeError"""
+        not hold raises BpeError.  errors: "replace" or "hold" returns a str instead, as decode_rows describes; with
+        "hold" (text, held uint32[1])."""
         ids = np.ascontiguousarray(ids, dtype=np.uint32).reshape(-1)
         v = self.vocab
-        out, _ = self._eng().decode_docs(ids, [0, ids.size], v.merges, v.specials or None, vocab=v)
-        return out
+        res = self._texts(self._eng().decode_docs(ids, [0, ids.size], v.merges, v.specials or None, vocab=v, errors=errors), 1, errors)
+        return (res[0][0],) + res[1:] if len(res) > 1 else res[0][0]
