@@ -274,6 +274,44 @@ int bpe_gpu_long_piece_info(uint64_t *out2);
    (left to the fallback), the largest number of rounds of one such document, workgroups launched}; all 0 when
    that kernel did not run.  BPE_GPU_ESTATE where bpe_gpu_docs_info returns it. */
 int bpe_gpu_long_info(bpe_gpu_ctx *ctx, uint64_t *out4);
+
+/* ------------------------------------------------------------------------
+ * Dropout.  BPE-dropout (Provilkov et al. 2020, Algorithm 1) on the device: a
+ * drop probability p in [0, 1] and a 64-bit seed give every document (piece) a
+ * segmentation of its own, a fresh one for every seed.
+ *   - Every document is replayed on its own, in rounds t = 0, 1, 2, ...
+ *   - In round t every adjacent pair of live tokens that has a rank is a
+ *     candidate.  A pair never crosses a document start.
+ *   - Each candidate is dropped or kept independently by a stateless draw:
+ *       thr = min(2^32, floor(p * 2^32)), a 64-bit value
+ *       k_t = low 32 bits of mix64(seed + 0x9E3779B97F4A7C15 * (t + 1)), computed mod 2^64, where
+ *             mix64(x): x ^= x >> 33; x *= 0xff51afd7ed558ccd; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53; x ^= x >> 33
+ *       g   = the resident byte offset of the first byte of the pair's left token (a batch is at most
+ *             2^32 - 2 bytes, so g fits 32 bits)
+ *       x = (uint32)g ^ k_t; x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16
+ *       the pair is dropped iff (uint64)x < thr
+ *   - If the round has no kept candidate (no pair has a rank, or every candidate was dropped) the document
+ *     is finished and takes no part in later rounds.  So p = 1 returns the bytes, and a document of k bytes
+ *     runs at most k rounds.
+ *   - Otherwise the smallest rank among the kept candidates wins.  All its kept occurrences merge left to
+ *     right; an occurrence whose left token is the right token of an occurrence just merged is skipped (in a
+ *     run a a a ... under a merge (a, a) the kept winners form stretches of consecutive kept positions, and
+ *     those at an even distance from their stretch's head merge).  Dropped winners stay as they are and are
+ *     drawn anew in round t + 1.
+ *   - With p = 0 the ids are those of BPE_ENC_PIECE_LONG, id for id.
+ *   - A document longer than bpe_gpu_long_piece_info's limit (16,384 bytes) goes through the per-document
+ *     fallback and is encoded WITHOUT dropout, and bpe_gpu_docs_info counts it in word 1 as always: this is
+ *     regularization, and the deterministic ids of one overlong document are valid ids.
+ * g is a position in the resident buffer: a text inside a batch draws differently from the same text
+ * encoded alone or elsewhere in a batch.  The same batch and the same seed give the same ids.
+ *
+ * p == 0: exactly the path of the _mode function, the window encoder included.  p outside [0, 1] or NaN:
+ * BPE_GPU_EINVAL.  p > 0 with BPE_ENC_WINDOW or BPE_ENC_PIECE: BPE_GPU_EINVAL.  p > 0 with BPE_ENC_AUTO or
+ * BPE_ENC_PIECE_LONG: always the piece-local replay (stats.enc_path 4) by the two dropout kernels;
+ * BPE_GPU_ERANGE beyond bpe_gpu_piece_info's id limit.  The calls set no state in the context.
+ * ---------------------------------------------------------------------- */
+int bpe_gpu_encode_docs_dropout(bpe_gpu_ctx *ctx, const uint64_t *doc_off, size_t ndocs,
+                                const uint32_t *pairs, size_t n_merges, int mode, double p, uint64_t seed);
 /* bpe_gpu_decode plus byte_off[0..ndocs] (bytes of document d = out[byte_off[d], byte_off[d+1])) */
 int bpe_gpu_decode_docs(bpe_gpu_ctx *ctx, const uint32_t *ids, size_t len, const uint64_t *id_off,
                         size_t ndocs, const uint32_t *pairs, size_t n_merges,
@@ -479,6 +517,10 @@ int bpe_gpu_fetch_split_offsets(bpe_gpu_ctx *ctx, uint64_t *out, size_t cap, siz
 int bpe_gpu_encode_split(bpe_gpu_ctx *ctx, const uint32_t *pairs, size_t n_merges);
 /* ... with the encoder chosen (BPE_ENC_*, see bpe_gpu_encode_docs_mode) */
 int bpe_gpu_encode_split_mode(bpe_gpu_ctx *ctx, const uint32_t *pairs, size_t n_merges, int mode);
+/* ... under dropout ("Dropout" above: the same rules for p, seed and mode); special pieces and a text batch's
+   gap bytes are handled exactly as bpe_gpu_encode_split_mode handles them, so a special keeps its one id */
+int bpe_gpu_encode_split_dropout(bpe_gpu_ctx *ctx, const uint32_t *pairs, size_t n_merges, int mode,
+                                 double p, uint64_t seed);
 
 /* ------------------------------------------------------------------------
  * Training on the pieces of the last split: merges that never cross a piece

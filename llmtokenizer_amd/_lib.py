@@ -41,7 +41,7 @@ EXPORTS = [
     # bpe_gpu.h: document batches
     "bpe_gpu_encode_docs", "bpe_gpu_fetch_doc_offsets", "bpe_gpu_docs_info", "bpe_gpu_decode_docs",
     "bpe_gpu_docs_window", "bpe_gpu_encode_docs_mode", "bpe_gpu_encode_split_mode", "bpe_gpu_piece_info",
-    "bpe_gpu_long_piece_info", "bpe_gpu_long_info",
+    "bpe_gpu_long_piece_info", "bpe_gpu_long_info", "bpe_gpu_encode_docs_dropout", "bpe_gpu_encode_split_dropout",
     "bpe_encode_docs_mode", "bpe_encode_split_mode",
     # bpe_gpu.h: splitting the resident bytes
     "bpe_gpu_split_rule", "bpe_gpu_split_info", "bpe_gpu_split", "bpe_gpu_fetch_split_offsets", "bpe_gpu_encode_split",
@@ -246,6 +246,8 @@ def load():
     L.bpe_encode_docs.restype = u32p
     L.bpe_gpu_encode_docs_mode.argtypes = [vp, vp, sz, vp, sz, ctypes.c_int]
     L.bpe_gpu_encode_split_mode.argtypes = [vp, vp, sz, ctypes.c_int]
+    L.bpe_gpu_encode_docs_dropout.argtypes = [vp, vp, sz, vp, sz, ctypes.c_int, ctypes.c_double, ctypes.c_uint64]
+    L.bpe_gpu_encode_split_dropout.argtypes = [vp, vp, sz, ctypes.c_int, ctypes.c_double, ctypes.c_uint64]
     L.bpe_gpu_piece_info.argtypes = [vp]
     L.bpe_gpu_long_piece_info.argtypes = [vp]
     L.bpe_gpu_long_info.argtypes = [vp, vp]

@@ -1305,15 +1305,23 @@ class Engine:
         m = np.ascontiguousarray(merges, dtype=np.uint32).reshape(-1)
         _lib.check(self.L.bpe_gpu_encode(self.ctx, m.ctypes.data_as(ctypes.c_void_p), m.size // 2), "encode")
 
-    def encode_docs(self, offsets, merges, encoder="window"):
+    def encode_docs(self, offsets, merges, encoder="window", dropout=0.0, seed=0):
         """encode the resident bytes as documents: document d is bytes
         [offsets[d], offsets[d + 1]) (bpe_gpu_encode_docs_mode); then ids(), doc_offsets(), docs_info().
         encoder: "window", "piece", "piece_long" or "auto", as in api.encode_batch; stats()["enc_path"] tells
-        which ran."""
+        which ran.  dropout (a probability in [0, 1]) and seed (taken mod 2^64): BPE-dropout, every document
+        segmented anew for every seed (bpe_gpu_encode_docs_dropout; the contract: bpe_gpu.h, "Dropout");
+        encoder "piece_long" or "auto" only, a document beyond long_piece_info()["piece_max"] is encoded
+        without it, and the draws are keyed by a token's byte offset in the batch."""
         off = _doc_offsets(offsets)
         if off.size < 1:
             raise BpeError("encode_docs: offsets must hold ndocs + 1 entries")
         m = np.ascontiguousarray(merges, dtype=np.uint32).reshape(-1)
+        if dropout != 0:
+            _lib.check(self.L.bpe_gpu_encode_docs_dropout(self.ctx, off.ctypes.data_as(ctypes.c_void_p), off.size - 1,
+                                                          m.ctypes.data_as(ctypes.c_void_p), m.size // 2, _encoder(encoder),
+                                                          float(dropout), int(seed) & 0xFFFFFFFFFFFFFFFF), "encode_docs")
+            return
         _lib.check(self.L.bpe_gpu_encode_docs_mode(self.ctx, off.ctypes.data_as(ctypes.c_void_p), off.size - 1,
                                                    m.ctypes.data_as(ctypes.c_void_p), m.size // 2, _encoder(encoder)),
                    "encode_docs")
@@ -1367,11 +1375,17 @@ class Engine:
                                                        n.value, ctypes.byref(n)), "fetch_special_pieces")
         return piece[: n.value], index[: n.value]
 
-    def encode_split(self, merges, encoder="window"):
+    def encode_split(self, merges, encoder="window", dropout=0.0, seed=0):
         """encode_docs over the last split's resident offsets (bpe_gpu_encode_split_mode);
         then ids(), doc_offsets(), docs_info() as after encode_docs.  After a split with specials
-        every special piece holds the one id 256 + len(merges) + j."""
+        every special piece holds the one id 256 + len(merges) + j.  dropout, seed: as in encode_docs
+        (bpe_gpu_encode_split_dropout); a special piece keeps its one id."""
         m = np.ascontiguousarray(merges, dtype=np.uint32).reshape(-1)
+        if dropout != 0:
+            _lib.check(self.L.bpe_gpu_encode_split_dropout(self.ctx, m.ctypes.data_as(ctypes.c_void_p), m.size // 2,
+                                                           _encoder(encoder), float(dropout),
+                                                           int(seed) & 0xFFFFFFFFFFFFFFFF), "encode_split")
+            return
         _lib.check(self.L.bpe_gpu_encode_split_mode(self.ctx, m.ctypes.data_as(ctypes.c_void_p), m.size // 2,
                                                     _encoder(encoder)), "encode_split")
 

@@ -92,6 +92,7 @@ struct EncPieceArgs {
     uint32_t *ctl;                   // [EPC_WORDS] long pieces, largest round count, internal error
     uint32_t *lng;                   // [tiles] the long pieces left out, in any order (nullptr: only counted)
     uint32_t tiles;
+    uint64_t thr, seed;              // dropout (encode_drop.hip): a pair is dropped iff its draw < thr; the rounds' seed
 };
 
 // the wave's own LDS stores and atomics are done before its next LDS loads

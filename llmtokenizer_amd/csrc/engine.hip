@@ -29,6 +29,7 @@
 #include "encode_docs.hip"
 #include "encode_piece.hip"
 #include "encode_long.hip"
+#include "encode_drop.hip"
 #include "split.hip"
 #include "split_o200k.hip"
 #include "train_split.hip"
@@ -2607,8 +2608,13 @@ EpTable ep_table(const uint32_t *pairs, size_t m, std::vector<uint32_t> &img) {
 // leaves them; *nlong = documents that have no ids yet: those longer than
 // EP_PIECE_MAX, or, with_long (k_enc_long behind the tiles, encode_long.hip),
 // those longer than EL_PIECE_MAX.  linfo: bpe_gpu_long_info's four words.
+// drop (with_long only): the two kernels of encode_drop.hip in their place.
+struct EpDrop {
+    uint64_t thr, seed;  // a pair is dropped iff its draw < thr (bpe_gpu.h, "Dropout")
+};
+
 int ep_run(bpe_gpu_ctx *c, const uint32_t *pairs, size_t n_merges, const uint64_t *d_doc, uint64_t ndocs, bool with_long,
-           uint64_t *nlong, uint64_t *tiles_out, uint64_t *rounds, uint64_t *linfo) {
+           const EpDrop *drop, uint64_t *nlong, uint64_t *tiles_out, uint64_t *rounds, uint64_t *linfo) {
     const uint64_t n = c->n0, tiles = (n + EP_C - 1) / EP_C;
     const uint64_t entries = with_long ? 2 * tiles : tiles;  // of (tfirst, tcnt): a long piece each behind the tiles'
     const uint32_t lgrid = with_long ? (uint32_t)std::min<uint64_t>(tiles, EL_GRID) : 0;
@@ -2644,10 +2650,19 @@ int ep_run(bpe_gpu_ctx *c, const uint32_t *pairs, size_t n_merges, const uint64_
     A.ctl = ctl;
     A.lng = lng;
     A.tiles = (uint32_t)tiles;
-    if (tiles) k_enc_piece<<<(uint32_t)tiles, EP_T, 0, c->st>>>(A);
-    HIPCHK(hipGetLastError());
-    if (lgrid) k_enc_long<<<lgrid, EL_T, 0, c->st>>>(A);  // (reads the list's length on the device)
-    HIPCHK(hipGetLastError());
+    if (drop) {
+        A.thr = drop->thr;
+        A.seed = drop->seed;
+        if (tiles) k_enc_piece_drop<<<(uint32_t)tiles, EP_T, 0, c->st>>>(A);
+        HIPCHK(hipGetLastError());
+        if (lgrid) k_enc_long_drop<<<lgrid, EL_T, 0, c->st>>>(A);
+        HIPCHK(hipGetLastError());
+    } else {
+        if (tiles) k_enc_piece<<<(uint32_t)tiles, EP_T, 0, c->st>>>(A);
+        HIPCHK(hipGetLastError());
+        if (lgrid) k_enc_long<<<lgrid, EL_T, 0, c->st>>>(A);  // (reads the list's length on the device)
+        HIPCHK(hipGetLastError());
+    }
     r = ROCPRIM_RUN(c, DS_SCAN_TMP, rocprim::exclusive_scan(tmp, tb, cnt, d_idoff, (uint64_t)0, ndocs + 1, rocprim::plus<uint64_t>(), c->st));
     if (r) return r;
     if (tiles)
@@ -3612,11 +3627,12 @@ int bpe_gpu_docs_window(const uint64_t *doc_off, size_t ndocs, uint64_t n, uint3
 // t_chk: when their check began) and bpe_gpu_encode_split (doc_off == nullptr:
 // the offsets are the split's, resident in c->d_split; the cold paths below
 // that read offsets on the host download them, and only they do).
+// drop: the piece-local replay under dropout (encode_drop.hip); the callers below have checked that the mode allows it.
 static int encode_docs_run(bpe_gpu_ctx *c, const uint64_t *doc_off, size_t ndocs, const uint32_t *pairs, size_t n_merges,
-                           double t_chk, int mode) {
+                           double t_chk, int mode, const EpDrop *drop = nullptr) {
     if (mode != BPE_ENC_WINDOW && mode != BPE_ENC_PIECE && mode != BPE_ENC_AUTO && mode != BPE_ENC_PIECE_LONG) return fail(BPE_GPU_EINVAL, "encode_docs: no such encoder mode");
     const bool ep_fits = 256 + (uint64_t)n_merges <= EP_MAX_IDS;
-    const bool piece_mode = mode == BPE_ENC_PIECE || mode == BPE_ENC_PIECE_LONG;
+    const bool piece_mode = mode == BPE_ENC_PIECE || mode == BPE_ENC_PIECE_LONG || drop;
     if (piece_mode && !ep_fits) return fail(BPE_GPU_ERANGE, "encode_docs: the merge list's ids exceed the piece-local replay's 2^21");
     const uint64_t n = c->n0;
     const bool resident = doc_off == nullptr;
@@ -3682,7 +3698,7 @@ static int encode_docs_run(bpe_gpu_ctx *c, const uint64_t *doc_off, size_t ndocs
     } else if (piece) {
         // the piece-local replay: only the documents longer than a tile (with_long: the long kernel) takes are left
         // for the fallback
-        if ((r = ep_run(c, pairs, n_merges, d_doc, ndocs, with_long, &nfailed, &tiles, &rounds, linfo))) return r;
+        if ((r = ep_run(c, pairs, n_merges, d_doc, ndocs, with_long, drop, &nfailed, &tiles, &rounds, linfo))) return r;
         first_pass = true;
         if (nfailed) {
             if ((r = host_offsets())) return r;
@@ -3767,10 +3783,21 @@ static int encode_docs_run(bpe_gpu_ctx *c, const uint64_t *doc_off, size_t ndocs
     return 0;
 }
 
-extern "C" {
+// The checks of a dropout call that need no context: 0 and *on (p > 0: *drop is set), or the error.
+static int dropout_args(const char *what, int mode, double p, uint64_t seed, EpDrop *drop, bool *on) {
+    if (!(p >= 0.0 && p <= 1.0)) return fail(BPE_GPU_EINVAL, (std::string(what) + ": the drop probability is not in [0, 1]").c_str());
+    *on = p > 0.0;
+    if (!*on) return 0;
+    if (mode == BPE_ENC_WINDOW || mode == BPE_ENC_PIECE)
+        return fail(BPE_GPU_EINVAL, (std::string(what) + (mode == BPE_ENC_WINDOW ? ": BPE_ENC_WINDOW" : ": BPE_ENC_PIECE") +
+                                     " has no dropout (BPE_ENC_PIECE_LONG or BPE_ENC_AUTO)").c_str());
+    drop->thr = p >= 1.0 ? 1ull << 32 : (uint64_t)(p * 4294967296.0);  // min(2^32, floor(p * 2^32))
+    drop->seed = seed;
+    return 0;
+}
 
-int bpe_gpu_encode_docs_mode(bpe_gpu_ctx *c, const uint64_t *doc_off, size_t ndocs, const uint32_t *pairs, size_t n_merges,
-                             int mode) {
+static int encode_docs_checked(bpe_gpu_ctx *c, const uint64_t *doc_off, size_t ndocs, const uint32_t *pairs, size_t n_merges,
+                               int mode, const EpDrop *drop) {
     if (!c || !doc_off || (!pairs && n_merges)) return BPE_GPU_EINVAL;
     if (!c->loaded) return fail(BPE_GPU_ESTATE, "encode before load");
     if (c->tx_on) return fail(BPE_GPU_ESTATE, "encode_docs: the context holds a text batch (bpe_gpu_load_texts): its gap bytes are no text; split it and use bpe_gpu_encode_split");
@@ -3783,7 +3810,22 @@ int bpe_gpu_encode_docs_mode(bpe_gpu_ctx *c, const uint64_t *doc_off, size_t ndo
     bool dec = false;  // (a reduction, not an early exit: 10^7 offsets are checked at memory speed)
     for (size_t d = 0; d < ndocs; d++) dec |= doc_off[d] > doc_off[d + 1];
     if (dec) return fail(BPE_GPU_EINVAL, "encode_docs: offsets decrease");
-    return encode_docs_run(c, doc_off, ndocs, pairs, n_merges, t_chk, mode);
+    return encode_docs_run(c, doc_off, ndocs, pairs, n_merges, t_chk, mode, drop);
+}
+
+extern "C" {
+
+int bpe_gpu_encode_docs_mode(bpe_gpu_ctx *c, const uint64_t *doc_off, size_t ndocs, const uint32_t *pairs, size_t n_merges,
+                             int mode) {
+    return encode_docs_checked(c, doc_off, ndocs, pairs, n_merges, mode, nullptr);
+}
+
+int bpe_gpu_encode_docs_dropout(bpe_gpu_ctx *c, const uint64_t *doc_off, size_t ndocs, const uint32_t *pairs, size_t n_merges,
+                                int mode, double p, uint64_t seed) {
+    EpDrop drop{};
+    bool on = false;
+    if (const int r = dropout_args("encode_docs_dropout", mode, p, seed, &drop, &on)) return r;
+    return encode_docs_checked(c, doc_off, ndocs, pairs, n_merges, mode, on ? &drop : nullptr);
 }
 
 int bpe_gpu_encode_docs(bpe_gpu_ctx *c, const uint64_t *doc_off, size_t ndocs, const uint32_t *pairs, size_t n_merges) {

@@ -398,7 +398,21 @@ int bpe_gpu_encode_split(bpe_gpu_ctx *c, const uint32_t *pairs, size_t n_merges)
     return bpe_gpu_encode_split_mode(c, pairs, n_merges, BPE_ENC_WINDOW);
 }
 
+static int encode_split_checked(bpe_gpu_ctx *c, const uint32_t *pairs, size_t n_merges, int mode, const EpDrop *drop);
+
 int bpe_gpu_encode_split_mode(bpe_gpu_ctx *c, const uint32_t *pairs, size_t n_merges, int mode) {
+    return encode_split_checked(c, pairs, n_merges, mode, nullptr);
+}
+
+int bpe_gpu_encode_split_dropout(bpe_gpu_ctx *c, const uint32_t *pairs, size_t n_merges, int mode, double p, uint64_t seed) {
+    EpDrop drop{};
+    bool on = false;
+    if (const int r = dropout_args("encode_split_dropout", mode, p, seed, &drop, &on)) return r;
+    return encode_split_checked(c, pairs, n_merges, mode, on ? &drop : nullptr);
+}
+
+// drop: the pieces replayed under dropout (encode_drop.hip); the special and break pieces' ids are replaced below either way
+static int encode_split_checked(bpe_gpu_ctx *c, const uint32_t *pairs, size_t n_merges, int mode, const EpDrop *drop) {
     if (!c || (!pairs && n_merges)) return BPE_GPU_EINVAL;
     if (!c->loaded) return fail(BPE_GPU_ESTATE, "encode before load");
     if (!c->split_ready) return fail(BPE_GPU_ESTATE, "encode_split: no split of the loaded bytes");
@@ -406,7 +420,7 @@ int bpe_gpu_encode_split_mode(bpe_gpu_ctx *c, const uint32_t *pairs, size_t n_me
     const bool tx = c->tx_on;
     const uint64_t M = c->sp_S || tx ? c->sp_M : 0;
     if (M && n_merges + 256 + c->sp_S > 0xFFFFFFFFull) return fail(BPE_GPU_ERANGE, "merge list too long for the specials' ids");
-    int r = encode_docs_run(c, nullptr, c->split_n, pairs, n_merges, now_ms(), mode);
+    int r = encode_docs_run(c, nullptr, c->split_n, pairs, n_merges, now_ms(), mode, drop);
     if (r || (!M && !tx)) return r;
     if (tx) c->docs_ready = false;  // (until the texts' offsets below are written)
     c->whole_ready = false;

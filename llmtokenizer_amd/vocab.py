@@ -254,7 +254,7 @@ class Vocab:
         if model.get("byte_fallback"):
             raise BpeError(f"{where}: byte_fallback is not supported")
         if model.get("dropout"):
-            raise BpeError(f"{where}: dropout ({model['dropout']}) is not supported")
+            raise BpeError(f"{where}: dropout ({model['dropout']}) is not taken from the file; pass it to Tokenizer(dropout=)")
         for key in ("continuing_subword_prefix", "end_of_word_suffix"):
             if model.get(key):
                 raise BpeError(f"{where}: {key} ({model[key]!r}) is not supported")
@@ -412,13 +412,26 @@ class Tokenizer:
     """Encode to and decode from a vocabulary's own ids on one GPU: the split of vocab.rule around
     vocab.specials, the merges applied inside the pieces, the ids rewritten on the device.  encoder: "auto"
     (the window encoder for a merge list within its limits, which encodes as before; the piece-local replay
-    for the longer lists of cl100k_base, Llama 3, Qwen2 and o200k_base), "window", "piece" or "piece_long" (api.encode_batch)."""
+    for the longer lists of cl100k_base, Llama 3, Qwen2 and o200k_base), "window", "piece" or "piece_long" (api.encode_batch).
+    dropout (a probability in [0, 1]) and seed: BPE-dropout for training data (the contract: bpe_gpu.h, "Dropout"):
+    every encode segments its pieces anew, on the device, by the piece-local replay (encoder "auto" or
+    "piece_long").  encode, encode_batch and encode_packed take seed=: an int is used as given, None stands for
+    the tokenizer's seed plus the number of dropout encodes it has made, so that epochs differ and a run
+    repeats.  A special keeps its id, a piece beyond 16,384 bytes is encoded without dropout, and the draws are
+    keyed by a token's byte offset in the batch: the same text draws differently at another place."""
 
-    def __init__(self, vocab, device=0, encoder="auto"):
+    def __init__(self, vocab, device=0, encoder="auto", dropout=0.0, seed=0):
         if encoder not in api.ENCODERS:
             raise api.BpeError(f"no encoder {encoder!r} (have {sorted(api.ENCODERS)})")
+        if not 0.0 <= dropout <= 1.0:  # (NaN too)
+            raise api.BpeError(f"dropout {dropout!r} is no probability in [0, 1]")
+        if dropout > 0 and encoder in ("window", "piece"):
+            raise api.BpeError(f'dropout needs the encoder "auto" or "piece_long", not {encoder!r}')
         self.vocab = vocab
         self.encoder = encoder
+        self.dropout = float(dropout)
+        self.seed = int(seed)
+        self._drops = 0  # dropout encodes made so far
         self.device = int(device)
         self._engine = None
 
@@ -449,11 +462,20 @@ class Tokenizer:
             e.normalize(v.normalizer)
         return n
 
+    def _encode_split(self, seed):
+        """the encode of every encode: over the split's pieces, under the tokenizer's dropout"""
+        e, v = self._eng(), self.vocab
+        if not self.dropout:
+            return e.encode_split(v.merges, encoder=self.encoder)
+        e.encode_split(v.merges, encoder=self.encoder, dropout=self.dropout,
+                       seed=self.seed + self._drops if seed is None else int(seed))
+        self._drops += 1
+
     def _spans(self, unit):
         v = self.vocab
         return self._eng().token_spans(v.merges, v.specials or None, vocab=v, unit=unit)
 
-    def encode(self, data, return_offsets=False, return_spans=None):
+    def encode(self, data, return_offsets=False, return_spans=None, seed=None):
         """uint32 vocabulary ids of data (bytes; a str is encoded as UTF-8).  return_offsets: also the id and
         byte offsets of the pieces, as api.encode_split returns them.  return_spans ("byte" or "char"): also, as
         the last element of the result, the span of every id in data, uint32[ids, 2], computed on the device: in
@@ -466,7 +488,7 @@ class Tokenizer:
         e, v = self._eng(), self.vocab
         self._load("encode", data, unit, batch=False)
         e.split(v.rule, v.specials or None)
-        e.encode_split(v.merges, encoder=self.encoder)
+        self._encode_split(seed)
         e.map_ids(v)
         ids = e.ids()
         out = (ids, e.doc_offsets(), e.split_offsets()) if return_offsets else (ids,)
@@ -475,7 +497,7 @@ class Tokenizer:
         return out if len(out) > 1 else ids
 
     def encode_batch(self, texts, max_length=None, pad_id=None, truncation_side="right", return_tensors=None,
-                     return_spans=None):
+                     return_spans=None, seed=None):
         """Encode a list of texts (bytes; a str is encoded as UTF-8) in one pass, each exactly as encode() does it
         alone: no piece, special or merge reaches from one text into the next, and an empty text has no id.
         Without max_length: (ids, text_off), text k's ids being ids[text_off[k]:text_off[k + 1]] (text_off uint64,
@@ -512,7 +534,7 @@ class Tokenizer:
         e, v = self._eng(), self.vocab
         n_texts = self._load("encode_batch", texts, unit)
         e.split(v.rule, v.specials or None)
-        e.encode_split(v.merges, encoder=self.encoder)
+        self._encode_split(seed)
         e.map_ids(v)
         if max_length is None:
             out = (e.ids(), e.text_offsets())
@@ -542,7 +564,8 @@ class Tokenizer:
         return int(self.vocab.special_ids[specials.index(name)])
 
     def encode_packed(self, texts, seq_len, pad_id, bos=None, eos=None, drop_last=False, return_segments=False,
-                      return_positions=False, return_tensors=None, whole=False, return_placement=False):
+                      return_positions=False, return_tensors=None, whole=False, return_placement=False,
+                      seed=None):
         """Encode a list of texts as encode_batch() does and lay the ids out for training (Engine.pack_stream; the
         contract: bpe_gpu.h, "Packed streams"): every text wrapped in bos / eos (None: without; an int is taken as
         a vocabulary id, a str or bytes must be one of vocab.specials and stands for its id), the texts joined end to
@@ -577,7 +600,7 @@ class Tokenizer:
         e, v = self._eng(), self.vocab
         self._load("encode_packed", texts)
         e.split(v.rule, v.specials or None)
-        e.encode_split(v.merges, encoder=self.encoder)
+        self._encode_split(seed)
         e.map_ids(v)
         if whole:
             R, N, _ = e.whole_rows(seq_len, bos_id, eos_id)

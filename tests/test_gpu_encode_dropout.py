@@ -1,0 +1,179 @@
+"""BPE-dropout on the device (encode_drop.hip; encode_docs / encode_split / Tokenizer with dropout=, seed=).
+The yardstick is _replay below: the contract of bpe_gpu.h, "Dropout", written out over lists of ids and byte
+offsets, the draw in Python ints.  Every comparison is exact equality of ids and id offsets."""
+import json
+import os
+import random
+
+import numpy as np
+import pytest
+
+import encode_limits_lib as EL
+import golden_lib as G
+from llmtokenizer_amd import api
+from llmtokenizer_amd.api import BpeError
+from llmtokenizer_amd.vocab import Tokenizer, Vocab
+
+pytestmark = pytest.mark.gpu
+
+M32, M64 = (1 << 32) - 1, (1 << 64) - 1
+
+
+def _mix64(x):
+    x ^= x >> 33
+    x = x * 0xff51afd7ed558ccd & M64
+    x ^= x >> 33
+    x = x * 0xc4ceb9fe1a85ec53 & M64
+    return x ^ x >> 33
+
+
+def _dropped(g, kt, thr):
+    x = (g ^ kt) & M32
+    x ^= x >> 16
+    x = x * 0x7feb352d & M32
+    x ^= x >> 15
+    x = x * 0x846ca68b & M32
+    return (x ^ x >> 16) < thr
+
+
+def _replay(piece, base, rank, p, seed):
+    """the ids of one piece whose first byte lies at resident offset base"""
+    thr = min(1 << 32, int(p * 4294967296.0))
+    ids, off, t = list(piece), list(range(base, base + len(piece))), 0
+    while True:
+        kt = _mix64((seed + 0x9E3779B97F4A7C15 * (t + 1)) & M64) & M32
+        kept = [(rank[ids[i], ids[i + 1]], i) for i in range(len(ids) - 1)
+                if (ids[i], ids[i + 1]) in rank and not _dropped(off[i], kt, thr)]
+        if not kept:
+            return ids
+        r = min(kept)[0]
+        win = {i for q, i in kept if q == r}
+        out, oo, i = [], [], 0
+        while i < len(ids):
+            merge = i in win
+            out.append(256 + r if merge else ids[i])
+            oo.append(off[i])
+            i += 2 if merge else 1
+        ids, off, t = out, oo, t + 1
+
+
+def _rank(merges):
+    return {tuple(m): r for r, m in reversed(list(enumerate(merges.tolist())))}
+
+
+def _encode(docs, merges, **kw):
+    e = api.Engine(0)
+    try:
+        e.load(b"".join(docs))
+        e.encode_docs(np.cumsum([0] + [len(d) for d in docs]).astype(np.uint64), merges, encoder="piece_long", **kw)
+        return e.ids().tolist(), e.doc_offsets().tolist(), e.docs_info(), e.stats()
+    finally:
+        e.close()
+
+
+def _letters(seed, n, alphabet=b"abcd"):
+    rng = random.Random(seed)
+    return bytes(rng.choice(alphabet) for _ in range(n))
+
+
+RUNS = np.array([[97, 97], [256, 256], [98, 97], [97, 98]], dtype=np.uint32)
+LETTERS = EL._random_merges(random.Random(5), b"abcd", 60, eq=0.2)
+BATCHES = {
+    # pieces of 1, 2 and 3 bytes and empty ones between them
+    "tiny": (RUNS, [b"a", b"", b"aa", b"", b"", b"aab", b"b", b"ba", b"", b"aaa", b"ab"]),
+    # a-runs of 2 to 9 that end inside and at the end of their piece; one of 150 over many lanes' ranges (the
+    # tile holds some 300 positions, 5 a lane), broken once; one that the long kernel's threads share
+    "runs": (RUNS, [b"a" * k + b"b" for k in range(2, 10)] + [b"b" + b"a" * k for k in range(2, 10)] +
+             [b"ba" + b"a" * 150 + b"b" + b"a" * 31, b"a" * 1500 + b"b" + b"a" * 777]),
+    # pieces across the 1,024-byte core edges and the lanes' ranges of full tiles
+    "straddle": (LETTERS, [_letters(i, n) for i, n in enumerate([700, 500, 37, 1, 0, 785, 1024, 3, 1021, 2, 600])]),
+    # a tile's longest piece, the long kernel's shortest, a piece its threads share unevenly, and its longest
+    "lengths": (LETTERS, [_letters(7, 1024), _letters(8, 1025), b"ab", _letters(9, 2500)]),
+    "limit": (RUNS, [b"b", b"a" * 16384, b"ab"]),
+}
+
+
+@pytest.mark.parametrize("seed", [0, 0xDEADBEEFCAFEF00D])
+@pytest.mark.parametrize("p", [0.1, 0.5])
+@pytest.mark.parametrize("name", list(BATCHES))
+def test_equals_the_replay(name, p, seed):
+    merges, docs = BATCHES[name]
+    rank, want, base = _rank(merges), [], 0
+    for d in docs:
+        want.append(_replay(d, base, rank, p, seed))
+        base += len(d)
+    ids, off, info, st = _encode(docs, merges, dropout=p, seed=seed)
+    assert off == np.cumsum([0] + [len(w) for w in want]).tolist()
+    assert ids == [x for w in want for x in w]
+    assert st["enc_path"] == 4 and info["docs_fallback"] == 0
+
+
+def test_seeds_differ():
+    merges, docs = BATCHES["straddle"]
+    a = _encode(docs, merges, dropout=0.1, seed=1)[0]
+    assert a != _encode(docs, merges, dropout=0.1, seed=2)[0] and a == _encode(docs, merges, dropout=0.1, seed=1)[0]
+
+
+def test_beyond_the_long_kernel_without_dropout():
+    docs = [b"ab", _letters(3, 16385), _letters(4, 300)]
+    det, doff, _, _ = _encode(docs, LETTERS)
+    ids, off, info, _ = _encode(docs, LETTERS, dropout=0.5, seed=9)
+    rank = _rank(LETTERS)
+    assert info["docs_fallback"] == 1
+    assert ids[off[1]:off[2]] == det[doff[1]:doff[2]]
+    assert ids[:off[1]] == _replay(docs[0], 0, rank, 0.5, 9)
+    assert ids[off[2]:] == _replay(docs[2], 2 + 16385, rank, 0.5, 9) != det[doff[2]:]
+
+
+@pytest.mark.parametrize("name", ["runs", "lengths"])
+def test_p0_and_p1(name):
+    merges, docs = BATCHES[name]
+    det = _encode(docs, merges)
+    assert _encode(docs, merges, dropout=0.0, seed=5)[:2] == det[:2]
+    ids, off, _, st = _encode(docs, merges, dropout=1.0, seed=5)
+    assert ids == list(b"".join(docs)) and off == np.cumsum([0] + [len(d) for d in docs]).tolist() and st["enc_path"] == 4
+
+
+def test_refusals():
+    e = api.Engine(0)
+    try:
+        e.load(b"abab")
+        for kw in ({"encoder": "window", "dropout": 0.1}, {"encoder": "piece", "dropout": 0.1},
+                   {"encoder": "piece_long", "dropout": 1.5}, {"encoder": "auto", "dropout": float("nan")}):
+            with pytest.raises(BpeError, match="invalid argument"):
+                e.encode_docs([0, 4], RUNS, **kw)
+        e.encode_docs([0, 4], RUNS, encoder="window", dropout=0.0)  # p = 0: the window encoder as ever
+        assert e.stats()["enc_path"] == 1
+    finally:
+        e.close()
+    for enc in ("window", "piece"):
+        with pytest.raises(BpeError):
+            Tokenizer(None, encoder=enc, dropout=0.1)
+
+
+def test_tokenizer(tmp_path):
+    with open(os.path.join(G.GOLD, "vocab", "vocab_gpt2u.json"), encoding="utf-8") as f:
+        fx = json.load(f)
+    path = tmp_path / "tokenizer.json"
+    path.write_text(json.dumps(fx["tokenizer_json"], ensure_ascii=False), encoding="utf-8")
+    v = Vocab.from_tokenizer_json(path)
+    texts = [t for t in fx["texts"] if t][:12]
+    big = " ".join(texts)
+    tk, tk2, plain = Tokenizer(v, dropout=0.3, seed=11), Tokenizer(v, dropout=0.3, seed=11), Tokenizer(v)
+    try:
+        first = tk.encode(big)
+        assert tk.decode(first) == big.encode("utf-8")
+        assert first.size > plain.encode(big).size  # (dropped merges leave more ids)
+        second = tk.encode(big)  # seed None: the next of the sequence
+        assert second.tolist() != first.tolist()
+        assert [tk2.encode(big).tolist(), tk2.encode(big).tolist()] == [first.tolist(), second.tolist()]
+        assert tk.encode(big, seed=11).tolist() == first.tolist()
+        ids, toff, spans = tk.encode_batch(texts, return_spans="byte")
+        assert tk.decode_batch(ids, toff) == [t.encode("utf-8") for t in texts]
+        for k, t in enumerate(texts):
+            s = spans[int(toff[k]):int(toff[k + 1])].tolist()
+            assert [a for a, _ in s] + [len(t.encode("utf-8"))] == [0] + [b for _, b in s], t
+        rows, n = tk.encode_packed(texts, 16, 0)
+        assert n > plain.encode_packed(texts, 16, 0)[1]
+    finally:
+        tk.close(), tk2.close(), plain.close()
