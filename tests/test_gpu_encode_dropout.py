@@ -1,5 +1,5 @@
 """BPE-dropout on the device (encode_drop.hip; encode_docs / encode_split / Tokenizer with dropout=, seed=).
-The yardstick is _replay below: the contract of bpe_gpu.h, "Dropout", written out over lists of ids and byte
+The yardstick is dropout_ref._replay: the contract of bpe_gpu.h, "Dropout", written out over lists of ids and byte
 offsets, the draw in Python ints.  Every comparison is exact equality of ids and id offsets."""
 import json
 import os
@@ -10,55 +10,12 @@ import pytest
 
 import encode_limits_lib as EL
 import golden_lib as G
+from dropout_ref import _rank, _replay
 from llmtokenizer_amd import api
 from llmtokenizer_amd.api import BpeError
 from llmtokenizer_amd.vocab import Tokenizer, Vocab
 
 pytestmark = pytest.mark.gpu
-
-M32, M64 = (1 << 32) - 1, (1 << 64) - 1
-
-
-def _mix64(x):
-    x ^= x >> 33
-    x = x * 0xff51afd7ed558ccd & M64
-    x ^= x >> 33
-    x = x * 0xc4ceb9fe1a85ec53 & M64
-    return x ^ x >> 33
-
-
-def _dropped(g, kt, thr):
-    x = (g ^ kt) & M32
-    x ^= x >> 16
-    x = x * 0x7feb352d & M32
-    x ^= x >> 15
-    x = x * 0x846ca68b & M32
-    return (x ^ x >> 16) < thr
-
-
-def _replay(piece, base, rank, p, seed):
-    """the ids of one piece whose first byte lies at resident offset base"""
-    thr = min(1 << 32, int(p * 4294967296.0))
-    ids, off, t = list(piece), list(range(base, base + len(piece))), 0
-    while True:
-        kt = _mix64((seed + 0x9E3779B97F4A7C15 * (t + 1)) & M64) & M32
-        kept = [(rank[ids[i], ids[i + 1]], i) for i in range(len(ids) - 1)
-                if (ids[i], ids[i + 1]) in rank and not _dropped(off[i], kt, thr)]
-        if not kept:
-            return ids
-        r = min(kept)[0]
-        win = {i for q, i in kept if q == r}
-        out, oo, i = [], [], 0
-        while i < len(ids):
-            merge = i in win
-            out.append(256 + r if merge else ids[i])
-            oo.append(off[i])
-            i += 2 if merge else 1
-        ids, off, t = out, oo, t + 1
-
-
-def _rank(merges):
-    return {tuple(m): r for r, m in reversed(list(enumerate(merges.tolist())))}
 
 
 def _encode(docs, merges, **kw):
